@@ -31,10 +31,18 @@ runs the same launcher / rendezvous / sharding / gather path on the CPU over
 gloo without the engine (the summaries count the descriptors only), for
 tests/test_bench_launch.py.
 
-The CPU baseline is the oracle (the C restatement of the reference path: SSE4.2
-CRC32C, liblz4 / libzstd / snappy through the reference's wrapper loops) on
-a bounded sample of the same workload, on this host's cores: 1 thread and T
-threads (T = the cores this job may use), median of 5 runs after a warm-up.
+A plain run does what the headline figure needs and no more: it builds the
+arena, warms up, times `--steps` steps and prints the result line.
+`--dump-outputs DIR` also writes what the last timed step computed (see
+dump_outputs).  Everything else runs only with `--full`:
+
+  - the CPU baseline: the oracle (the C restatement of the reference path:
+    SSE4.2 CRC32C, liblz4 / libzstd / snappy through the reference's wrapper
+    loops) on a bounded sample of the same workload, on this host's cores: 1
+    thread and T threads (T = the cores this job may use), median of 5 runs
+    after a warm-up, and the comparison of the GPU's timed output with it;
+  - `--full-check`: every batch of a decompress config against the oracle
+    (on by default for c5).
 
 Prints ONE JSON line on rank 0 (contract in the task statement).
 """
@@ -252,6 +260,79 @@ def index_slices_equal(g_index, g_first, g_count, w_index, w_first, w_count) -> 
     return True
 
 
+# ---- --dump-outputs: what the last timed step computed ----------------------------------------
+DUMP_BATCHES = 32768          # batches per result table (all of them if the rank has no more)
+DUMP_INDEX_ENTRIES = 131072   # index entries per index table
+DUMP_OUT_BYTES = 4 << 20      # bytes of rewritten batches
+DUMP_LIMIT = 64 << 20         # bytes of .npy data in all
+
+
+def dump_sample(n: int) -> np.ndarray:
+    """The batches a dump holds: all n, or a fixed seeded sample of DUMP_BATCHES
+    of them (ascending, the first and the last batch always among them)."""
+    if n <= DUMP_BATCHES:
+        return np.arange(n, dtype=np.int64)
+    pick = np.random.default_rng(0x5EED0D).choice(n, DUMP_BATCHES, replace=False)
+    pick[:2] = (0, n - 1)
+    return np.unique(pick).astype(np.int64)
+
+
+def fields_f64(a: np.ndarray) -> np.ndarray:
+    """A structured array as float64 [rows, fields], in the dtype's field order.
+    Every field is an integer; values up to 2^53 (all CRCs, counts, lengths and
+    the generator's offsets and timestamps) are exact."""
+    return np.stack([a[f].astype(np.float64) for f in a.dtype.names], axis=1)
+
+
+def index_rows(d_index, first: np.ndarray, count: np.ndarray):
+    """The index entries (32 B rows of the device index) of the leading batches of
+    (first, count) that fit in DUMP_INDEX_ENTRIES, batch after batch, so the table
+    does not depend on where the slices lie.  Returns (rows as INDEX_DTYPE, batches)."""
+    import torch
+
+    from redpanda_amd import abi
+
+    rows_all = d_index.numel() // 32
+    first, count = first.astype(np.int64), count.astype(np.int64)
+    k = int(np.searchsorted(np.cumsum(count), DUMP_INDEX_ENTRIES, side="right"))
+    inside = (count[:k] == 0) | (first[:k] + count[:k] <= rows_all)
+    if not inside.all():  # a slice outside the index: keep the batches before it
+        k = int(np.argmin(inside))
+    rows = (np.concatenate([np.arange(f, f + c) for f, c in zip(first[:k], count[:k])])
+            if k and count[:k].sum() else np.zeros(0, dtype=np.int64))
+    sel = torch.from_numpy(rows).to(d_index.device)
+    got = d_index.view(rows_all, 32).index_select(0, sel).cpu().numpy()
+    return got.reshape(-1).view(abi.INDEX_DTYPE), k
+
+
+def out_bytes_of(d_out, offset: np.ndarray, length: np.ndarray):
+    """The bytes [offset, offset + length) of the leading batches that fit in
+    DUMP_OUT_BYTES, concatenated.  Returns (uint8 array, batches)."""
+    import torch
+
+    offset, length = offset.astype(np.int64), length.astype(np.int64)
+    k = int(np.searchsorted(np.cumsum(length), DUMP_OUT_BYTES, side="right"))
+    inside = offset[:k] + length[:k] <= d_out.numel()
+    if not inside.all():
+        k = int(np.argmin(inside))
+    parts = [d_out[a:a + m] for a, m in zip(offset[:k].tolist(), length[:k].tolist()) if m > 0]
+    got = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.uint8)
+    return got, k
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """Writes each array as path/<name>.npy (float32 / float64 only), at most
+    DUMP_LIMIT bytes in all."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the limit of {DUMP_LIMIT}")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log(f"[dump] {len(arrays)} arrays, {total / 2**20:.1f} MiB in {path}")
+
+
 # ---- rank launcher (--gpus N without torchrun) -------------------------------------------
 def launch_ranks(nranks: int, argv: list[str]) -> int:
     """Start `nranks` copies of this script as ranks 0..N-1 of one job (RANK /
@@ -391,12 +472,19 @@ def main() -> int:
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"])
     ap.add_argument("--batches", type=int, default=0, help="override batches per GPU (weak) / in total (strong)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also time the CPU baseline, compare the timed output with the "
+                         "oracle on a sample and run --full-check; a run without it only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64 / float32; "
+                         "DIR/rank<r>/ for the other ranks of a multi-GPU job)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--cpu-runs", type=int, default=5)
     ap.add_argument("--ops", type=int, default=0, help="override the rpgpu_op mask (diagnostics)")
     ap.add_argument("--full-check", type=int, default=-1,
-                    help="compare every batch of a decompress config with the oracle (default: on for c5)")
+                    help="with --full: compare every batch of a decompress config with the oracle "
+                         "(default: on for c5)")
     ap.add_argument("--payload", default="text", choices=["text", "alnum"],
                     help="record payload of the compressed configs (text: Zipf words, alnum: random)")
     ap.add_argument("--walk-chunks", type=int, default=0, help="rpgpu_opts.walk_chunks (tuning; 0 = default)")
@@ -412,6 +500,10 @@ def main() -> int:
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU only: launcher, gloo rendezvous, sharding and the summary gather, no engine")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.full_check > 0 and not args.full:
+        ap.error("--full-check 1 needs --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -662,12 +754,51 @@ def main() -> int:
         except (OSError, ValueError):
             pass
 
+    # ---- --dump-outputs: the last timed step's outputs, as a caller receives them --------
+    if args.dump_outputs:
+        pick = dump_sample(n)
+        idx, idx_batches = index_rows(d_index, res["index_first"][pick], res["index_count"][pick])
+        arrays = {
+            # the gathered per-partition summaries (shard.FIELDS; twice for the decompress
+            # configs: input batches, rewritten batches) -- every batch counts in them
+            "summaries": summary.astype(np.float64),
+            "batch_ids": pick.astype(np.float64),                  # rows of the tables below
+            "results": fields_f64(res[pick]),                      # abi.RESULT_DTYPE fields
+            "index_used": np.array([float(d_used.item())]),
+            # abi.INDEX_DTYPE fields of the first index_batches sampled batches' entries
+            "index": fields_f64(idx),
+            "index_batches": np.array([float(idx_batches)]),
+        }
+        if decompress:
+            okd = dres["verdict"][pick] == abi.V_OK
+            dsel = dres[pick].copy()
+            dsel["out_len"][~okd] = 0  # defined for the decoded ones only
+            osel = d_odescs.cpu().numpy().view(abi.DESC_DTYPE)[pick].copy()
+            osel[~okd] = 0  # likewise
+            okp = pick[okd]
+            oidx, oidx_batches = index_rows(d_index2, ores["index_first"][pick], ores["index_count"][pick])
+            obytes, ob_batches = out_bytes_of(d_out, dres["out_offset"][okp], 61 + dres["out_len"][okp])
+            arrays.update({
+                "decomp_results": fields_f64(dsel),                # abi.DECOMP_RESULT_DTYPE fields
+                "decomp_counts": d_obytes.cpu().numpy().astype(np.float64),  # output bytes, index entries
+                "rewritten_descs": fields_f64(osel),
+                "rewritten_results": fields_f64(ores[pick]),
+                "rewritten_index": fields_f64(oidx),
+                "rewritten_index_batches": np.array([float(oidx_batches)]),
+                # header + decoded records of the first rewritten_batches decoded sampled batches
+                "rewritten_bytes": obytes.astype(np.float32),
+                "rewritten_batches": np.array([float(ob_batches)]),
+            })
+        dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"), arrays)
+
     # ---- CPU baseline: the oracle on this host's cores, bounded sample -----------------
     # the CPU baseline is timed on rank 0 at N=1 only (the other ranks would sit in
     # the job's teardown while it runs, and the host cores are shared by N ranks)
     if world > 1:
         out["cpu_baseline_note"] = "timed at --gpus 1 only"
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if not args.full:
+        out["cpu_baseline_note"] = "timed with --full only"
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle.oracle as orc
 
         T, hostinfo = effective_cores()
@@ -783,7 +914,7 @@ def main() -> int:
         out["gpu_checked_batches"] = checked
 
     full = args.full_check if args.full_check >= 0 else int(args.config == "c5")
-    if decompress and full:
+    if args.full and decompress and full:
         # every batch's verdicts, decoded length, rewritten batch
         # (its results: CRCs of the decoded bytes) and index against the oracle
         out["full_check"] = full_check(spec, chunks, part_shift, res, dres, ores,

@@ -7,5 +7,5 @@ run() {  # name, limit, args
   timeout -k 10 $2 python bench.py $3 > gpurun_out/r5final/$1.json 2> gpurun_out/r5final/$1.err || { tail -5 gpurun_out/r5final/$1.err; return 1; }
   python -c "import json;d=json.load(open('gpurun_out/r5final/$1.json'));print('$1', d['value'], d['unit'], d['ms_per_step'], d['roofline']['frac'], (d.get('cpu_baseline') or {}).get('value'), d.get('gpu_matches_oracle_on_all_batches', d.get('gpu_matches_oracle_on_sample')))"
 }
-run c2 300 "--config c2" && run c1 300 "--config c1" && run c3 400 "--config c3 --steps 5 --warmup 2" \
-  && run c5 500 "--config c5 --steps 5 --warmup 2" && run c4 400 "--config c4 --steps 3 --warmup 1"
+run c2 300 "--full --config c2" && run c1 300 "--full --config c1" && run c3 400 "--full --config c3 --steps 5 --warmup 2" \
+  && run c5 500 "--full --config c5 --steps 5 --warmup 2" && run c4 400 "--full --config c4 --steps 3 --warmup 1"

@@ -19,10 +19,10 @@ unset RPGPU_DIAG_LIB
 timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method thread tests/test_gpu_decomp.py tests/test_gpu_bench_configs.py tests/test_gpu_append_time.py > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
 for r in 1 2; do
-  timeout -k 10 900 python -u bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline --full-check 1 > $O/c4_full$r.json 2> $O/c4_full$r.err || { tail -5 $O/c4_full$r.err; exit 1; }
+  timeout -k 10 900 python -u bench.py --full --config c4 --steps 3 --warmup 1 --no-cpu-baseline --full-check 1 > $O/c4_full$r.json 2> $O/c4_full$r.err || { tail -5 $O/c4_full$r.err; exit 1; }
   python -c "import json; d=json.load(open('$O/c4_full$r.json')); print('c4', d['ms_per_step'], d['roofline']['kernel_ms'], d['full_check']['batches'], d['full_check']['mismatched_batches'])"
 done
-timeout -k 10 900 python -u bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline --full-check 1 > $O/c5_full.json 2> $O/c5_full.err || { tail -5 $O/c5_full.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full --config c5 --steps 3 --warmup 1 --no-cpu-baseline --full-check 1 > $O/c5_full.json 2> $O/c5_full.err || { tail -5 $O/c5_full.err; exit 1; }
 python -c "import json; d=json.load(open('$O/c5_full.json')); print('c5', d['ms_per_step'], d['full_check']['batches'], d['full_check']['mismatched_batches'])"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c4 -o run -- python bench.py --config c4 --steps 3 --warmup 1 --no-cpu-baseline > $O/prof_c4.json 2> $O/prof_c4.err || { tail -5 $O/prof_c4.err; exit 1; }
 f=$(find $O/prof_c4 -name "*kernel_stats.csv" | head -1); cp "$f" $O/c4_kernel_stats.csv
