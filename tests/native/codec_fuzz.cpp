@@ -448,6 +448,25 @@ int main(int argc, char** argv) {
             return 0;
         }
     }
+    for (int a = 1; a + 1 < argc; a += 2) {
+        if (strcmp(argv[a], "--frames")) continue;  // CODEC:FILE -- frames (u32 length + bytes each), each checked every way
+        int codec = 0;
+        char path[4096];
+        if (sscanf(argv[a + 1], "%d:%4095s", &codec, path) != 2) return 2;
+        FILE* fp = fopen(path, "rb");
+        if (!fp) return 2;
+        uint32_t n;
+        long id = 0;
+        while (fread(&n, 4, 1, fp) == 1) {
+            Bytes f(n);
+            if (n && fread(f.data(), 1, n, fp) != n) return 2;
+            check(codec, f, "frames", id++);
+        }
+        fclose(fp);
+        printf("frames: %ld cases, %ld decoded, %ld rejected, %ld split plans (%ld taken): engine == oracle\n", n_cases,
+               n_ok, n_rejected, n_split, n_split_ok);
+        return 0;
+    }
     rng.seed(seed);
     for (long c = 0; c < cases; c++) {
         const uint64_t kind = below(20);

@@ -153,6 +153,20 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[a], "--exact")) g_exact = atoi(argv[a + 1]) != 0;
     }
     rng.seed(seed);
+    for (int a = 1; a + 1 < argc; a += 2) {
+        if (strcmp(argv[a], "--frames")) continue;  // FILE: frames (u32 length + bytes each) against the oracle
+        FILE* fp = fopen(argv[a + 1], "rb");
+        if (!fp) return 2;
+        uint32_t n;
+        while (fread(&n, 4, 1, fp) == 1) {
+            Bytes f(n);
+            if (n && fread(f.data(), 1, n, fp) != n) return 2;
+            compare(f);
+        }
+        fclose(fp);
+        printf("frames: %ld cases, %ld decoded, %ld rejected: engine == oracle\n", n_cases, n_ok, n_rejected);
+        return 0;
+    }
     for (long i = 0; i < cases; i++) {
         const size_t sizes[] = {0, 1, 20, 300, 5000, 70000, 200000};
         const Bytes f = zframe(payload(below(4) ? below(sizes[below(7)] + 1) : sizes[below(7)]));

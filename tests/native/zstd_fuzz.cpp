@@ -35,6 +35,7 @@ unsigned FSE_isError(size_t code);
 size_t FSE_writeNCount(void* buf, size_t cap, const short* norm, unsigned maxSV, unsigned tableLog);
 size_t FSE_normalizeCount(short* norm, unsigned tableLog, const unsigned* count, size_t total, unsigned maxSV);
 uint32_t HUF_selectDecoder(size_t dstSize, size_t cSrcSize);
+size_t HUF_compress(void* dst, size_t cap, const void* src, size_t n);
 }
 
 namespace {
@@ -493,27 +494,48 @@ Bytes ring_frame() {
     return out;
 }
 
-// One compressed block: raw literals, then the given sequences with the
-// predefined FSE tables (the bitstream written last-first as
-// ZSTD_encodeSequences does; rpgpu_zstdc.h's encoder pieces).
-Bytes seq_block(const Bytes& lits, const std::vector<rpzstdc::Seq>& seqs) {
+// One compressed block: raw literals (`huf`: Huffman-compressed by libzstd's
+// HUF_compress, four streams -- falling back to raw when they do not
+// compress), then the given sequences with the predefined FSE tables (the
+// bitstream written last-first as ZSTD_encodeSequences does; rpgpu_zstdc.h's
+// encoder pieces).  `ofv`: Seq.off holds the offset value itself (1..3: a
+// repeat-offset code) instead of the offset.
+Bytes seq_block(const Bytes& lits, const std::vector<rpzstdc::Seq>& seqs, bool ofv_given = false, bool huf = false) {
     static rpzstdc::Ws w;
     static bool init = false;
     if (!init) rpzstdc::init_tables(w), init = true;
-    Bytes out(lits.size() + 64 + 16 * seqs.size());
+    const uint32_t add = ofv_given ? 0u : 3u;
+    Bytes out(lits.size() + 512 + 16 * seqs.size());
     const uint32_t nlit = (uint32_t)lits.size();
-    out[0] = (uint8_t)((3u << 2) | ((nlit & 15) << 4));  // raw, 20-bit size
-    out[1] = (uint8_t)(nlit >> 4);
-    out[2] = (uint8_t)(nlit >> 12);
-    uint64_t o = 3;
-    for (uint8_t c : lits) out[o++] = c;
+    uint64_t o = 0;
+    size_t hsize = 0;
+    if (huf && nlit >= 64 && nlit < (1u << 18)) {
+        hsize = HUF_compress(out.data() + 5, out.size() - 5, lits.data(), nlit);
+        if (ZSTD_isError(hsize) || hsize <= 1 || hsize >= nlit) hsize = 0;
+    }
+    if (hsize) {  // compressed, 4 streams, 18-bit sizes: a 5-byte header
+        const uint64_t h = 2u | (3u << 2) | ((uint64_t)nlit << 4) | ((uint64_t)hsize << 22);
+        for (int k = 0; k < 5; k++) out[k] = (uint8_t)(h >> (8 * k));
+        o = 5 + hsize;
+    } else {
+        out[0] = (uint8_t)((3u << 2) | ((nlit & 15) << 4));  // raw, 20-bit size
+        out[1] = (uint8_t)(nlit >> 4);
+        out[2] = (uint8_t)(nlit >> 12);
+        o = 3;
+        for (uint8_t c : lits) out[o++] = c;
+    }
     const uint32_t nseq = (uint32_t)seqs.size();
-    out[o++] = (uint8_t)nseq;  // < 128
-    out[o++] = 0;              // LL, OF, ML: predefined
+    if (nseq < 128) {
+        out[o++] = (uint8_t)nseq;
+    } else {  // < 0x7F00: two bytes
+        out[o++] = (uint8_t)((nseq >> 8) + 128);
+        out[o++] = (uint8_t)nseq;
+    }
+    out[o++] = 0;  // LL, OF, ML: predefined
     rpzstdc::BitW b{out.data(), o, 0, 0};
     rpzstdc::CState sll, sof, sml;
     const rpzstdc::Seq& last = seqs[nseq - 1];
-    uint32_t llc = rpzstdc::ll_code(last.ll), mlc = rpzstdc::ml_code(last.ml), ofv = last.off + 3,
+    uint32_t llc = rpzstdc::ll_code(last.ll), mlc = rpzstdc::ml_code(last.ml), ofv = last.off + add,
              ofc = rpzstdc::hb32(ofv);
     rpzstdc::init_state(sml, w.ml, mlc);
     rpzstdc::init_state(sof, w.of, ofc);
@@ -523,7 +545,7 @@ Bytes seq_block(const Bytes& lits, const std::vector<rpzstdc::Seq>& seqs) {
     b.add(ofv, ofc);
     for (uint32_t k = nseq - 1; k-- > 0;) {
         const rpzstdc::Seq& q = seqs[k];
-        llc = rpzstdc::ll_code(q.ll), mlc = rpzstdc::ml_code(q.ml), ofv = q.off + 3, ofc = rpzstdc::hb32(ofv);
+        llc = rpzstdc::ll_code(q.ll), mlc = rpzstdc::ml_code(q.ml), ofv = q.off + add, ofc = rpzstdc::hb32(ofv);
         rpzstdc::encode_sym(b, sof, w.of, ofc);
         rpzstdc::encode_sym(b, sml, w.ml, mlc);
         rpzstdc::encode_sym(b, sll, w.ll, llc);
@@ -723,6 +745,88 @@ Bytes span_frame(uint32_t lead, uint32_t ll, uint32_t len1, uint32_t m2) {
 }
 
 long n_span = 0, n_span_ok = 0;
+// Frames over the sequence geometries of tests/seq_frames.py
+// (zstd_geometry_file: per frame u32 blocks, flags, pad; per block u32
+// sequences, literals, the literal bytes, then ll / ml / offset value as u32
+// each): every block a compressed block of raw (flags & 1: Huffman) literals
+// and predefined-table sequences, the literals past the last sequence as the
+// block's trailing literals; then `pad` bytes of RLE blocks (a large slot for
+// four bytes per 128 KiB).  With a content size (single segment) unless
+// flags & 2: then a 1 MiB window.
+bool seqgrid(const char* in_path, const char* out_path) {
+    FILE* fi = fopen(in_path, "rb");
+    if (!fi) return false;
+    Bytes g;
+    for (int c; (c = fgetc(fi)) != EOF;) g.push_back((uint8_t)c);
+    fclose(fi);
+    FILE* fo = fopen(out_path, "wb");
+    if (!fo) return false;
+    size_t p = 0;
+    auto u32 = [&]() {
+        uint32_t v = 0;
+        if (p + 4 <= g.size()) memcpy(&v, &g[p], 4);
+        p += 4;
+        return v;
+    };
+    while (p + 12 <= g.size()) {
+        const uint32_t nblocks = u32(), flags = u32(), pad = u32();
+        Bytes body;
+        uint64_t total = pad;
+        for (uint32_t k = 0; k < nblocks; k++) {
+            const uint32_t nseq = u32(), nlit = u32();
+            if (p + nlit + 12ull * nseq > g.size() || nseq == 0 || nseq >= 0x7F00) return false;
+            const Bytes lits(g.begin() + p, g.begin() + p + nlit);
+            p += nlit;
+            std::vector<rpzstdc::Seq> seqs(nseq);
+            uint64_t size = nlit;
+            for (auto& q : seqs) {
+                q.ll = u32(), q.ml = u32(), q.off = u32();
+                size += q.ml;
+            }
+            total += size;
+            const Bytes blk = seq_block(lits, seqs, true, (flags & 1) != 0);
+            const uint32_t last = (k + 1 == nblocks && pad == 0) ? 1u : 0u;
+            const uint32_t bh = last | (2u << 1) | ((uint32_t)blk.size() << 3);
+            body.push_back((uint8_t)bh), body.push_back((uint8_t)(bh >> 8)), body.push_back((uint8_t)(bh >> 16));
+            body.insert(body.end(), blk.begin(), blk.end());
+        }
+        for (uint32_t left = pad; left;) {
+            const uint32_t n = left < (128u << 10) ? left : (128u << 10);
+            left -= n;
+            const uint32_t bh = (left ? 0u : 1u) | (1u << 1) | (n << 3);
+            body.push_back((uint8_t)bh), body.push_back((uint8_t)(bh >> 8)), body.push_back((uint8_t)(bh >> 16));
+            body.push_back((uint8_t)('p' + (left >> 17)));
+        }
+        Bytes f = {0x28, 0xB5, 0x2F, 0xFD};
+        if (flags & 2) {
+            f.push_back(0x00), f.push_back((uint8_t)((20 - 10) << 3));
+        } else {
+            f.push_back(0xA0);  // single segment, 4-byte content size
+            put32(f, (uint32_t)total);
+        }
+        f.insert(f.end(), body.begin(), body.end());
+        const uint32_t n = (uint32_t)f.size();
+        if (fwrite(&n, 4, 1, fo) != 1 || fwrite(f.data(), 1, n, fo) != n) return false;
+    }
+    return fclose(fo) == 0 && p == g.size();
+}
+
+// --frames FILE: frames (u32 length + bytes each) against the oracle
+bool check_frames(const char* path) {
+    FILE* fp = fopen(path, "rb");
+    if (!fp) return false;
+    uint32_t n;
+    while (fread(&n, 4, 1, fp) == 1) {
+        Bytes f(n);
+        if (n && fread(f.data(), 1, n, fp) != n) return false;
+        compare(f);
+    }
+    fclose(fp);
+    printf("frames: %ld cases (%ld through the ring pass), %ld decoded, %ld rejected, %ld block plans (%ld decoded): "
+           "engine == oracle\n", n_cases, n_ring, n_ok, n_rejected, n_blk, n_blk_ok);
+    return true;
+}
+
 void check_span(long cases) {
     const long ok0 = n_ok;
     for (uint32_t lead : {0u, 1u, 3u})
@@ -810,6 +914,14 @@ int main(int argc, char** argv) {
             }
             fclose(fp);
             return 0;
+        }
+        if (!strcmp(argv[a], "--dump-seqgrid")) {  // GEOMETRY: its frames (u32 length + bytes each) to seqgrid.bin
+            rng.seed(seed);
+            return seqgrid(argv[a + 1], "seqgrid.bin") ? 0 : 2;
+        }
+        if (!strcmp(argv[a], "--frames")) {
+            rng.seed(seed);
+            return check_frames(argv[a + 1]) ? 0 : 2;
         }
         if (!strcmp(argv[a], "--dump-span")) {  // RANDOM: span frames (u32 length + bytes each) to span.bin
             rng.seed(seed);

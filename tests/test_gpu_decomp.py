@@ -14,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(__file__))
 from kafka_batches import DISK, WIRE, arena, batch, record  # noqa: E402
+from seq_frames import lz4_frame, lz4_run_block  # noqa: E402
 
 import oracle.oracle as orc  # noqa: E402
 
@@ -558,31 +559,6 @@ def test_split_fallback_below_wave_size(eng):
     got = eng.decompress_arena(data, descs)
     want = compare(got, data, descs)
     assert want["verdicts"][0] == abi.V_DECOMP_ERROR and want["verdicts"][1] == abi.V_OK
-
-
-def lz4_frame(blocks, content=None):
-    """An LZ4 frame (independent 64 KiB blocks, no checksums) around the given
-    compressed blocks, with or without a content size."""
-    import struct
-
-    import xxhash
-
-    desc = bytes([0x60 | (0x08 if content is not None else 0), 0x40])
-    desc += struct.pack("<Q", content) if content is not None else b""
-    f = struct.pack("<I", 0x184D2204) + desc + bytes([(xxhash.xxh32(desc, seed=0).intdigest() >> 8) & 0xFF])
-    for b in blocks:
-        f += struct.pack("<I", len(b)) + b
-    return f + b"\0\0\0\0"
-
-
-def lz4_run_block(n, c=b"a", tail=b"12345"):
-    """An LZ4 block decoding to n bytes: c, a run of it (offset 1), then tail."""
-    import struct
-
-    def ext(r):
-        return b"\xff" * (r // 255) + bytes([r % 255])
-
-    return bytes([0x1F]) + c + struct.pack("<H", 1) + ext(n - 1 - len(tail) - 4 - 15) + bytes([len(tail) << 4]) + tail
 
 
 def test_split_short_block_frames(eng):
