@@ -18,29 +18,12 @@
 // Plain C++: the same decision code runs on the device (rpgpu_decomp.hip,
 // executed uniformly by a wavefront whose emitter runs the copies with all
 // lanes, rpgpu_wave.h) and on the host in the differential fuzz test against
-// the oracle (tests/native/codec_fuzz.cpp, DirectEmit).  Direct copies move up
-// to 64 bytes per step and may run up to 63 bytes past the end of a sequence
-// (later sequences overwrite those bytes, as liblz4's own wild copies do), so
-// an output buffer needs kSlack writable bytes past its planned capacity and
-// an input buffer 64 readable bytes past its end (RPGPU_ARENA_TAIL_PAD).
+// the oracle (tests/native/codec_fuzz.cpp, DirectEmit).  The copies and how
+// far each may read and write past its ranges (kSlack, kInPad): rpgpu_copy.h.
 #ifndef RPGPU_CODEC_H
 #define RPGPU_CODEC_H
 
-#include <stdint.h>
-#include <string.h>
-
-#ifdef __HIPCC__
-#define RPC_HD __host__ __device__ __forceinline__
-#else
-#define RPC_HD static inline
-#endif
-// member functions (a static specifier does not apply to them on the host)
-#if defined(__HIPCC__)
-#define RPC_MF __host__ __device__ __forceinline__
-#else
-#define RPC_MF inline
-#endif
-
+#include "rpgpu_copy.h"
 
 namespace rpcodec {
 
@@ -49,172 +32,6 @@ constexpr uint64_t kMaxChunk = 128u * 1024u;  // details::io_allocation_size::ma
 // verdicts (include/rpgpu.h)
 constexpr int32_t V_OK = 0, V_UNDEFINED = 11, V_ERROR = 30, V_TRAILING = 32, V_UNSUPPORTED = 33,
                   V_OVERFLOW = 34;
-
-// 16 bytes as a vector value (a struct with an array member would be kept in
-// scratch memory by the device compiler when live across branches)
-typedef uint32_t B16 __attribute__((vector_size(16)));
-RPC_HD void ld16(B16& v, const uint8_t* p) { __builtin_memcpy(&v, p, 16); }
-RPC_HD void st16(uint8_t* p, const B16& v) { __builtin_memcpy(p, &v, 16); }
-RPC_HD uint32_t le16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-RPC_HD uint32_t le32(const uint8_t* p) {
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-RPC_HD uint64_t le64(const uint8_t* p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-RPC_HD uint32_t be32(const uint8_t* p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-// dst[0, n) = src[0, n) for ranges that do not overlap within 64 bytes:
-// 64 bytes per step, four loads in flight
-RPC_HD void copy_fwd(uint8_t* dst, const uint8_t* src, uint64_t n) {
-    if (n <= 16) {
-        if (n) {
-            B16 v;
-            ld16(v, src);
-            st16(dst, v);
-        }
-        return;
-    }
-    for (uint64_t i = 0; i < n; i += 64) {
-        B16 a, b, c, d;
-        ld16(a, src + i);
-        ld16(b, src + i + 16);
-        ld16(c, src + i + 32);
-        ld16(d, src + i + 48);
-        st16(dst + i, a);
-        st16(dst + i + 16, b);
-        st16(dst + i + 32, c);
-        st16(dst + i + 48, d);
-    }
-}
-
-// LZ77 back-reference: dst[i] = dst[i - off] in increasing i, i.e. the
-// period-`off` extension of the `off` bytes before dst.  off == 0 yields
-// zeros, which is what liblz4's offset-0 copy produces (LZ4_write32(op, 0)
-// before the self-copy).
-RPC_HD void copy_match(uint8_t* dst, uint64_t off, uint64_t n) {
-    if (off >= 64) {
-        copy_fwd(dst, dst - off, n);  // each 64-byte source block is already written
-        return;
-    }
-    if (off >= 16) {
-        for (uint64_t i = 0; i < n; i += 16) {
-            B16 v;
-            ld16(v, dst - off + i);
-            st16(dst + i, v);
-        }
-        return;
-    }
-    // 16-byte pattern: the `off` bytes before dst repeated (two 64-bit
-    // halves, doubled by shifts; no per-byte array, which would live in
-    // scratch memory on the device)
-    uint64_t lo = 0, hi = 0, step = 16;
-    if (off != 0) {
-        const uint8_t* s = dst - off;
-        lo = le64(s);
-        hi = le64(s + 8);
-        if (off <= 8) {
-            if (off < 8) lo &= (1ull << (8 * off)) - 1;
-            hi = 0;
-        } else {
-            hi &= (1ull << (8 * (off - 8))) - 1;
-        }
-        for (uint64_t w = off; w < 16; w *= 2) {
-            const uint64_t sh = 8 * w;  // 8..120 bits
-            if (sh < 64) {
-                hi |= (hi << sh) | (lo >> (64 - sh));
-                lo |= lo << sh;
-            } else {
-                hi |= lo << (sh - 64);
-            }
-        }
-        step = off * (16 / off);  // a whole number of periods
-    }
-    B16 p;
-    p[0] = (uint32_t)lo;
-    p[1] = (uint32_t)(lo >> 32);
-    p[2] = (uint32_t)hi;
-    p[3] = (uint32_t)(hi >> 32);
-    for (uint64_t i = 0; i < n; i += step) st16(dst + i, p);
-}
-
-// n < 16 bytes of lo|hi, exactly
-RPC_HD void st_part(uint8_t* p, uint64_t lo, uint64_t hi, uint64_t n) {
-    if (n & 8) {
-        __builtin_memcpy(p, &lo, 8);
-        p += 8;
-        lo = hi;
-    }
-    if (n & 4) {
-        const uint32_t v = (uint32_t)lo;
-        __builtin_memcpy(p, &v, 4);
-        p += 4;
-        lo >>= 32;
-    }
-    if (n & 2) {
-        const uint16_t v = (uint16_t)lo;
-        __builtin_memcpy(p, &v, 2);
-        p += 2;
-        lo >>= 16;
-    }
-    if (n & 1) *p = (uint8_t)lo;
-}
-// Exact copies (nothing written past dst + n), for outputs whose next bytes
-// another lane may already have written (split blocks and chunks).
-RPC_HD void copy_exact(uint8_t* dst, const uint8_t* src, uint64_t n) {  // disjoint ranges
-    uint64_t i = 0;
-    for (; i + 16 <= n; i += 16) {
-        B16 v;
-        ld16(v, src + i);
-        st16(dst + i, v);
-    }
-    if (i < n) st_part(dst + i, le64(src + i), le64(src + i + 8), n - i);
-}
-RPC_HD void match_exact(uint8_t* dst, uint64_t off, uint64_t n) {  // dst[i] = dst[i - off]; off 0: zeros
-    if (off >= 16) {
-        uint64_t i = 0;
-        for (; i + 16 <= n; i += 16) {
-            B16 v;
-            ld16(v, dst - off + i);
-            st16(dst + i, v);
-        }
-        if (i < n) st_part(dst + i, le64(dst - off + i), le64(dst - off + i + 8), n - i);
-        return;
-    }
-    uint64_t lo = 0, hi = 0, step = 16;
-    if (off != 0) {
-        const uint8_t* s = dst - off;
-        lo = le64(s);
-        hi = le64(s + 8);
-        if (off <= 8) {
-            if (off < 8) lo &= (1ull << (8 * off)) - 1;
-            hi = 0;
-        } else {
-            hi &= (1ull << (8 * (off - 8))) - 1;
-        }
-        for (uint64_t w = off; w < 16; w *= 2) {
-            const uint64_t sh = 8 * w;
-            if (sh < 64) {
-                hi |= (hi << sh) | (lo >> (64 - sh));
-                lo |= lo << sh;
-            } else {
-                hi |= lo << (sh - 64);
-            }
-        }
-        step = off * (16 / off);
-    }
-    B16 p;
-    p[0] = (uint32_t)lo, p[1] = (uint32_t)(lo >> 32), p[2] = (uint32_t)hi, p[3] = (uint32_t)(hi >> 32);
-    uint64_t i = 0;
-    for (; i + 16 <= n; i += step) st16(dst + i, p);
-    if (i < n) st_part(dst + i, lo, hi, n - i);
-}
 
 // ---------------------------------------------------------------- emitters
 // The decoders below decide everything -- acceptance, lengths, offsets --
@@ -470,51 +287,11 @@ RPC_HD int64_t lz4_block(E& em, const uint8_t* in, int64_t isz, uint8_t* out, in
 // store); this form spends one:
 //   - tokens, lengths and offsets are read from a 64-byte register window
 //     whose next 32 bytes are prefetched a step ahead;
-//   - a sequence with <= 32 literal bytes and a match of <= 32 bytes whose
-//     source lies before it (offset >= 16 per 16-byte chunk), or any match
-//     with offset < 16 (a period rebuilt in registers), issues all its loads
-//     at once -- literal bytes, the match source's chunks -- and composes the
-//     match bytes that come from this sequence's own literal run from
-//     registers (those bytes are not stored yet when the loads issue);
-//   - the stores follow (16-byte wild stores as liblz4's, each sequence's
-//     overwriting the previous one's overshoot).
-// Longer runs take lz4_block's copies.  Host-compiled by the differential
-// fuzz test (tests/native/codec_fuzz.cpp) against the oracle.
-#ifndef RPGPU_LZ4_WC  // write-combined output stores in lz4_block_lane
-#define RPGPU_LZ4_WC 1
-#endif
-struct V16 {
-    uint64_t lo, hi;
-};
-RPC_HD V16 v16_ld(const uint8_t* p) {
-    B16 v;
-    ld16(v, p);
-    return V16{((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2]};
-}
-RPC_HD void v16_st(uint8_t* p, const V16& x) {
-    B16 v;
-    v[0] = (uint32_t)x.lo, v[1] = (uint32_t)(x.lo >> 32), v[2] = (uint32_t)x.hi, v[3] = (uint32_t)(x.hi >> 32);
-    st16(p, v);
-}
-RPC_HD uint64_t funnel(uint64_t a, uint64_t b, uint32_t s) {  // bytes [s, s + 8) of a|b, s < 8
-    return s ? (a >> (8 * s)) | (b << (64 - 8 * s)) : a;
-}
-// bytes [r, r + 16) of the 32 bytes x|y (bytes past 32 read as zero), r < 32
-RPC_HD V16 v16_ext(const V16& x, const V16& y, uint32_t r) {
-    const uint32_t k = r >> 3, s = r & 7;
-    const uint64_t a = k == 0 ? x.lo : k == 1 ? x.hi : k == 2 ? y.lo : y.hi;
-    const uint64_t b = k == 0 ? x.hi : k == 1 ? y.lo : k == 2 ? y.hi : 0;
-    const uint64_t c = k == 0 ? y.lo : k == 1 ? y.hi : 0;
-    return V16{funnel(a, b, s), funnel(b, c, s)};
-}
-// x moved up by t bytes (t <= 16), zeros shifted in
-RPC_HD V16 v16_shl(const V16& x, uint32_t t) { return v16_ext(V16{0, 0}, x, 16 - t); }
-// bytes [0, k) of a, [k, 16) of b (k <= 16)
-RPC_HD V16 v16_merge(const V16& a, const V16& b, uint32_t k) {
-    const uint64_t ml = k >= 8 ? ~0ull : (1ull << (8 * k)) - 1;
-    const uint64_t mh = k >= 16 ? ~0ull : k > 8 ? (1ull << (8 * (k - 8))) - 1 : 0ull;
-    return V16{(a.lo & ml) | (b.lo & ~ml), (a.hi & mh) | (b.hi & ~mh)};
-}
+//   - a short sequence issues all its loads at once -- literal bytes (from
+//     the window where they lie inside it), the match source's chunks -- and
+//     then its stores, write-combined (rpgpu_copy.h wc_exec).
+// Longer runs take exact copies.  Host-compiled by the differential fuzz test
+// (tests/native/codec_fuzz.cpp) against the oracle.
 
 // 64 input bytes [pos, pos + 64) in registers plus the next 32 in flight
 struct Win64 {
@@ -611,13 +388,6 @@ RPC_HD uint32_t w64_at(Win64& W, const uint8_t* in, int32_t p, int32_t need, int
     const uint32_t lo = w64_dword(W, q);
     return sh ? (lo >> sh) | (w64_dword(W, q + 1) << (32 - sh)) : lo;
 }
-// bytes of x (output offset xb) that lie in [pb, pb + 16) replaced by p's
-RPC_HD V16 v16_overlay(const V16& x, int32_t xb, const V16& p, int32_t pb) {
-    const int32_t e = pb - xb;  // x's byte e is p's byte 0
-    if (e >= 16 || e <= -16) return x;
-    if (e >= 0) return v16_merge(x, v16_shl(p, (uint32_t)e), (uint32_t)e);
-    return v16_merge(v16_ext(p, V16{0, 0}, (uint32_t)-e), x, (uint32_t)(16 + e));
-}
 RPC_HD uint32_t lz4_varlen64(Win64& W, const uint8_t* in, int32_t& ip, int32_t lencheck, bool initial_check,
                              int& err, int32_t lim) {
     uint32_t len = 0;
@@ -658,10 +428,7 @@ int32_t lz4_block_lane(const uint8_t* in, int32_t isz, uint8_t* out, int32_t oca
     int err;
     Win64 W;
     w64_load(W, in, 0, lim);
-#if RPGPU_LZ4_WC
-    V16 cur{0, 0}, cur1{0, 0};  // output [ca, op), not stored yet (op - ca < 32)
-    int32_t ca = 0;             // memory holds the output below ca
-#endif
+    WcBuf<int32_t> wc{};  // output [wc.ca, op), not stored yet
     for (;;) {
         // keep the token and the fields after it inside the window
         if (ip >= W.pos + 32) {
@@ -728,123 +495,22 @@ int32_t lz4_block_lane(const uint8_t* in, int32_t isz, uint8_t* out, int32_t oca
             }
         }
         // ---- copies
-        const bool pat = off < 16;
-        const int32_t nch = pat ? 1 : (ml + 15) >> 4;
-        if (last || ll > 32 || (!pat && (ml > 32 || off < 16 * nch)) || op_m + ml + 15 > oend) {
+        if (last || off == 0 || !wc_fits(ll, ml, off) || op_m + ml + 15 > oend) {
             // exact copies: nothing is written past the block's capacity
-            // (a split frame's next block may already be there)
-#if RPGPU_LZ4_WC
-            if (op - ca >= 16) {
-                v16_st(out + ca, cur);
-                if (op - ca > 16) st_part(out + ca + 16, cur1.lo, cur1.hi, (uint64_t)(op - ca - 16));
-            } else if (op > ca) {
-                st_part(out + ca, cur.lo, cur.hi, (uint64_t)(op - ca));
-            }
-#endif
+            // (a split frame's next block may already be there); offset 0
+            // (liblz4's zeros) is match_exact's
+            wc_flush(wc, out, op);
             if (ll) copy_exact(out + op, in + ip_lit, (uint64_t)ll);
             if (last) return op + ll;
             match_exact(out + op_m, (uint64_t)off, (uint64_t)ml);
             op = op_m + ml;
-#if RPGPU_LZ4_WC
-            ca = op;
-#endif
+            wc.ca = op;
             continue;
         }
-        // one round trip: every load of the sequence, then its stores
-        const int32_t rel = ll - off;  // match source start - literal start
-        const uint8_t* src = out + op_m - off;
-        V16 L0{0, 0}, L1{0, 0}, A0{0, 0}, A1{0, 0};
+        V16 L0{0, 0}, L1{0, 0};
         if (ll > 0) L0 = lit16(W, in, ip_lit);
         if (ll > 16) L1 = lit16(W, in, ip_lit + 16);
-        if (off != 0 && rel < 0) A0 = v16_ld(src);
-        if (!pat && nch > 1 && rel + 16 < 0) A1 = v16_ld(src + 16);
-#if RPGPU_LZ4_WC
-        if (op > ca && rel < 0) {
-            // source bytes in [ca, op) are still in cur | cur1 (bytes from op
-            // on are the literal run's, merged below)
-            const int32_t sb = op_m - off;
-            A0 = v16_overlay(v16_overlay(A0, sb, cur, ca), sb, cur1, ca + 16);
-            if (!pat && nch > 1 && rel + 16 < 0)
-                A1 = v16_overlay(v16_overlay(A1, sb + 16, cur, ca), sb + 16, cur1, ca + 16);
-        }
-#endif
-        // 16 source bytes at literal-relative r: stored bytes (A) below the
-        // literal run, the run's own bytes (registers) from it on
-        const int32_t r0 = rel, r1 = rel + 16;
-        const V16 c0 = r0 >= 0 ? v16_ext(L0, L1, (uint32_t)r0)
-                       : r0 <= -16 ? A0 : v16_merge(A0, v16_shl(L0, (uint32_t)-r0), (uint32_t)-r0);
-        V16 first = c0;  // the match's first 16 bytes
-        uint64_t step = 16;
-        if (pat) {
-            // period-off pattern (off 0: liblz4's zeros), stored a whole
-            // number of periods apart
-            uint64_t lo = 0, hi = 0;
-            if (off != 0) {
-                lo = c0.lo;
-                hi = c0.hi;
-                if (off <= 8) {
-                    if (off < 8) lo &= (1ull << (8 * off)) - 1;
-                    hi = 0;
-                } else {
-                    hi &= (1ull << (8 * (off - 8))) - 1;
-                }
-                for (uint64_t w = (uint64_t)off; w < 16; w *= 2) {
-                    const uint64_t sh = 8 * w;
-                    if (sh < 64) {
-                        hi |= (hi << sh) | (lo >> (64 - sh));
-                        lo |= lo << sh;
-                    } else {
-                        hi |= lo << (sh - 64);
-                    }
-                }
-                step = (uint64_t)off * (16 / (uint64_t)off);
-            }
-            first = V16{lo, hi};
-        }
-        if (ll + ml <= 16) {
-            // the whole sequence in one 16-byte store (most text sequences)
-            const V16 sq = ll ? v16_merge(L0, v16_shl(first, (uint32_t)ll), (uint32_t)ll) : first;
-#if RPGPU_LZ4_WC
-            // ... appended to `cur`; a store only when 16 bytes are complete
-            // (no store: the next sequence's loads wait for none)
-            const uint32_t f = (uint32_t)(op - ca);
-            if (f < 16) {  // f + ll + ml < 32: nothing to store
-                cur = f ? v16_merge(cur, v16_shl(sq, f), f) : sq;
-                cur1 = v16_ext(sq, V16{0, 0}, 16 - f);
-            } else {
-                const uint32_t g = f - 16;
-                const V16 c1 = g ? v16_merge(cur1, v16_shl(sq, g), g) : sq;
-                if (f + (uint32_t)(ll + ml) >= 32) {
-                    v16_st(out + ca, cur);
-                    v16_st(out + ca + 16, c1);
-                    cur = v16_ext(sq, V16{0, 0}, 16 - g);
-                    ca += 32;
-                } else {
-                    cur1 = c1;
-                }
-            }
-#else
-            v16_st(out + op, sq);
-#endif
-        } else {
-#if RPGPU_LZ4_WC
-            if (op > ca) v16_st(out + ca, cur);  // wild: the stores below overwrite [op, ca + 32)
-            if (op > ca + 16) v16_st(out + ca + 16, cur1);
-            ca = op_m + ml;
-#endif
-            if (ll > 0) v16_st(out + op, L0);
-            if (ll > 16) v16_st(out + op + 16, L1);
-            if (pat) {
-                for (uint64_t i = 0; i < (uint64_t)ml; i += step) v16_st(out + op_m + i, first);
-            } else {
-                v16_st(out + op_m, c0);
-                if (nch > 1) {
-                    const V16 c1 = r1 >= 0 ? v16_ext(L0, L1, (uint32_t)r1)
-                                   : r1 <= -16 ? A1 : v16_merge(A1, v16_shl(L0, (uint32_t)-r1), (uint32_t)-r1);
-                    v16_st(out + op_m + 16, c1);
-                }
-            }
-        }
+        wc_exec(wc, out, op, L0, L1, ll, ml, off);
         op = op_m + ml;
     }
 }

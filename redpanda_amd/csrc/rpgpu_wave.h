@@ -21,7 +21,7 @@
 // wave: vector memory operations of one wavefront go through one L1 in
 // program order, so a later load sees an earlier store with no fence (the
 // LLVM AMDGPU memory model needs no cache maintenance within a wavefront).
-// Every copy writes exactly its own bytes (rpzstd's exact copies), so lanes
+// Every copy writes exactly its own bytes (rpgpu_copy.h's exact copies), so lanes
 // of one round never overwrite each other.
 //
 // zstd's Huffman / RLE literals go to a per-wave scratch buffer (not the
@@ -80,7 +80,7 @@ __device__ __forceinline__ void coop_copy(uint8_t* dst, const uint8_t* src, uint
             if (i + 16 <= n) {
                 rpcodec::st16(dst + i, v);
             } else {
-                rpzstd::st_part(dst + i, ((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2], n - i);
+                rpcodec::st_part(dst + i, ((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2], n - i);
             }
         }
     }
@@ -99,7 +99,7 @@ __device__ __forceinline__ void coop_match(uint8_t* dst, uint64_t off, uint64_t 
             if (i + 16 <= n) {
                 rpcodec::st16(dst + i, v);
             } else {
-                rpzstd::st_part(dst + i, ((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2], n - i);
+                rpcodec::st_part(dst + i, ((uint64_t)v[1] << 32) | v[0], ((uint64_t)v[3] << 32) | v[2], n - i);
             }
         }
     }
@@ -115,7 +115,7 @@ __device__ __forceinline__ void coop_fill(uint8_t* dst, uint8_t b, uint64_t n, u
         if (i + 16 <= n) {
             rpcodec::st16(dst + i, p);
         } else if (i < n) {
-            rpzstd::st_part(dst + i, xx, xx, n - i);
+            rpcodec::st_part(dst + i, xx, xx, n - i);
         }
     }
 }
@@ -131,7 +131,7 @@ __device__ __forceinline__ void exec_seqs(uint8_t* gbase, bool v, const uint8_t*
     uint8_t* const o = gbase + (inc - tot);
     uint8_t* const mo = o + (v ? ll : 0);
     // literal runs: each lane its own, long ones wave-wide
-    if (v && ll && ll <= 64) rpzstd::copy_lits(o, lsrc, ll);
+    if (v && ll && ll <= 64) rpcodec::copy_lits(o, lsrc, ll);
     for (uint64_t m = ballot(v && ll > 64); m; m &= m - 1) {
         const uint32_t k = (uint32_t)__builtin_ctzll(m);
         coop_copy((uint8_t*)readlane64((uint64_t)o, k), (const uint8_t*)readlane64((uint64_t)lsrc, k),
@@ -147,9 +147,9 @@ __device__ __forceinline__ void exec_seqs(uint8_t* gbase, bool v, const uint8_t*
         const bool wide = ready && ml > 64 && off >= 64;
         if (ready && !wide) {
             if (off == 0)
-                rpzstd::fill_bytes(mo, 0, ml);  // liblz4's offset-0 copy: zeros
+                rpcodec::fill_bytes(mo, 0, ml);  // liblz4's offset-0 copy: zeros
             else
-                rpzstd::copy_seq_match(mo, off, ml);
+                rpcodec::copy_seq_match(mo, off, ml);
         }
         for (uint64_t m = ballot(wide); m; m &= m - 1) {
             const uint32_t k = (uint32_t)__builtin_ctzll(m);

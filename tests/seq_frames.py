@@ -1,6 +1,7 @@
 """Crafted frames whose LZ77 sequences walk the geometry space of the device
-copy engines (rpgpu_zstd.h wc_seq / copy_lits / copy_seq_match / match_exact,
-rpgpu_codec.h lz4_block_lane and the snappy decoders, rpgpu_wave.h exec_seqs /
+copy engines (rpgpu_copy.h wc_exec / period16 / copy_lits / copy_seq_match /
+copy_exact / match_exact / copy_match, under rpgpu_zstd.h wc_seq, rpgpu_codec.h
+lz4_block_lane and the snappy decoders, rpgpu_wave.h exec_seqs /
 coop_match / coop_copy, rpgpu_inflate.h Write::copy), and a plain
 byte-at-a-time model of what they decode to.
 
