@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define RPGPU_ABI_VERSION 5
+#define RPGPU_ABI_VERSION 6
 #define RPGPU_ARENA_TAIL_PAD 64
 #define RPGPU_HEADER_SIZE 61 /* model/record.h:527-540 */
 
@@ -114,6 +114,17 @@ enum rpgpu_verdict {
                                       offset below the offset-translation delta */
     RPGPU_V_SKIPPED = 40,          /* not decompressed: no RPGPU_OP_DECOMP, not
                                       validated OK, or not compressed        */
+    /* legacy MessageSets, produce versions below 3 (rpgpu_legacy_*; kafka/protocol/
+     * kafka_batch_adapter.cc:215-301, kafka/protocol/legacy_message.h) */
+    RPGPU_V_LEGACY_MAGIC = 50,           /* magic not 0 or 1: legacy_error            */
+    RPGPU_V_LEGACY_CRC_MISMATCH = 51,    /* CRC32 mismatch: legacy_error              */
+    RPGPU_V_LEGACY_LZ4_MAGIC0 = 52,      /* magic 0 with lz4: legacy_error            */
+    RPGPU_V_LEGACY_NULL_COMPRESSED = 53, /* compressed message, null value: legacy_error */
+    RPGPU_V_LEGACY_TRUNC_THROW = 54,     /* out_of_range escapes the message decoder  */
+    RPGPU_V_LEGACY_BAD_CODEC_THROW = 55, /* attributes & 7 in 4..7: runtime_error     */
+    RPGPU_V_LEGACY_COMPRESSED = 56,      /* a compressed wrapper message that passed its
+                                            own checks: the set is NOT converted, the
+                                            caller routes it to the reference path   */
 };
 
 /* Kafka error codes of the produce path (kafka/protocol/errors.h:22,29,47,227). */
@@ -543,6 +554,116 @@ int32_t rpgpu_record_sets_run_device(rpgpu_ctx* ctx, const rpgpu_batch_desc* d_s
                                      rpgpu_batch_result* d_batch_results, rpgpu_record_index* d_index,
                                      uint64_t index_cap, uint64_t* d_index_used, void* d_scratch,
                                      void* d_batch_scratch, void* hip_stream);
+
+/* ---- legacy MessageSets (produce versions 0..2) ------------------------------
+ * Replaces kafka_batch_adapter::adapt_with_version for version < 3
+ * (kafka/protocol/kafka_batch_adapter.cc:215-301): convert_message_set over
+ * decode_legacy_batch (kafka/protocol/legacy_message.h), record_batch_builder::
+ * add_raw_kv / build and reset_size_checksum_metadata
+ * (storage/parser_utils.cc:122-128).  d_sets[i] (an rpgpu_batch_desc, format
+ * RPGPU_FMT_KAFKA_WIRE, length < 2^31: the caller's duty, only
+ * rpgpu_convert_message_set checks it) is the record data of one produce
+ * partition: magic-0 / magic-1 messages back to back in one fragment.  A
+ * descriptor with RPGPU_DESC_NULL_RECORDS reads no bytes: RPGPU_V_NULL_RECORDS.
+ *
+ * The walk, per message, while bytes are left: int64 offset, int32
+ * batch_length, int32 crc (big-endian; a consume that lacks bytes throws,
+ * bytes/details/io_iterator_consumer.h:63-83: LEGACY_TRUNC_THROW, so 1..15
+ * trailing bytes throw); the CRC range is share_no_consume((size_t)
+ * batch_length - 4) right after the crc field, and iobuf::share clamps to the
+ * bytes left (bytes/iobuf.cc:162-185): batch_length < 4 covers everything
+ * left, a batch_length beyond the message covers the following ones, 4 is the
+ * CRC of nothing; int8 magic (not 0 / 1: LEGACY_MAGIC, before any CRC check);
+ * int8 attributes; magic 1: int64 timestamp; zlib CRC32 of the range
+ * (hashing/crc32.h:18-33) against crc (LEGACY_CRC_MISMATCH); int32 key size
+ * and key, int32 value size and value (-1 null; any other negative size or one
+ * past the set's end throws); the next message starts where the value ended
+ * (batch_length does not delimit it).  Then attributes & 7: 4..7
+ * LEGACY_BAD_CODEC_THROW; 0 the record is added; 1..3: magic 0 with lz4
+ * LEGACY_LZ4_MAGIC0, else a null value LEGACY_NULL_COMPRESSED, else
+ * LEGACY_COMPRESSED.  The first event in this order decides the set.
+ *
+ * RPGPU_V_LEGACY_COMPRESSED: the reference decompresses the wrapper's value and
+ * recurses; this engine does not (out of scope, as is fragmented input: DESIGN.md
+ * §3 and §7), so the set is not converted and the caller sends it down the reference's
+ * CPU path, as for a compaction scope over the key budget.
+ *
+ * A converted set is one on-disk batch: size_bytes 61 + body, base_offset 0,
+ * type raft_data, attrs 0, last_offset_delta n - 1 (-1 for an empty set, which
+ * converts to an empty batch), first_timestamp = max_timestamp = T (the last
+ * magic-1 timestamp, else now_ms, the caller's model::timestamp::now()),
+ * producer id / epoch / base sequence -1, record_count n, crc =
+ * crc_record_batch, header_crc = internal_header_only_crc; record i is
+ * vint(len) 00 vint(0) vint(i) vint(klen|-1) key vint(vlen|-1) value vint(0).
+ * Hand vector: message A (magic 1, ts 1600000000000, key "k", value "v")
+ *   0000000000000000 00000018 5eaf63dc 01 00 00000174876e8000 00000001 6b 00000001 76
+ * then B (magic 0, null key, value "hi", offset 1)
+ *   0000000000000001 00000010 fd6ebddb 00 00 ffffffff 00000002 6869
+ * give the body 10 00 00 00 02 6b 02 76 00 10 00 00 02 01 04 68 69 00, T =
+ * 1600000000000, n = 2.  A record's v2 framing is at most 23 bytes, the legacy
+ * framing at least 26, so the body never exceeds the set's length. */
+typedef struct rpgpu_legacy_result {
+    int32_t verdict;       /* OK, NULL_RECORDS, LEGACY_*, DECOMP_OVERFLOW         */
+    int32_t record_count;  /* records of the batch                               */
+    int32_t event_message; /* index of the deciding message; -1: OK, NULL_RECORDS,
+                              DECOMP_OVERFLOW                                    */
+    uint32_t codec;        /* attributes & 7 of that message (LEGACY_COMPRESSED), else 0 */
+    int64_t timestamp;     /* T                                                  */
+    uint64_t out_offset;   /* the batch in d_out                                 */
+    uint64_t out_len;      /* its bytes (61 + body)                              */
+    uint64_t out_cap;      /* bytes reserved for it                              */
+} rpgpu_legacy_result;     /* 48 bytes; a verdict other than OK specifies only
+                              verdict, event_message and codec */
+
+/* The same two-call shape and stream rules as rpgpu_decomp_*: plan, then run
+ * with the same d_scratch, a context's calls on one stream (or ordered with
+ * events).  Plan: *d_out_bytes = the output slots, then (256-byte aligned) the
+ * message table and work list the run keeps in d_out (64 bytes per message the walk
+ * reaches);
+ * the output buffer must hold *d_out_bytes + RPGPU_ARENA_TAIL_PAD bytes and
+ * be 16-byte aligned (RPGPU_EINVAL otherwise).
+ * *d_records_total = the index capacity the run needs.  Run: d_lres[i], the
+ * batches in d_out, and d_out_descs / d_out_results / d_index / *d_index_used
+ * exactly as rpgpu_decomp_run_device writes them (length 0, ops 0, verdict
+ * STREAM_SHORT where nothing was converted), so the output feeds
+ * rpgpu_run_device, fetch, compaction and compress unchanged.  A set whose slot
+ * does not fit out_cap gets RPGPU_V_DECOMP_OVERFLOW (reused: the output slot is
+ * too small), and so does every non-null set when the message table does not
+ * fit, because no checksum can then be checked. */
+size_t rpgpu_legacy_scratch_bytes(uint32_t nsets);
+int32_t rpgpu_legacy_plan_device(rpgpu_ctx* ctx, const rpgpu_batch_desc* d_sets, uint32_t nsets,
+                                 const uint8_t* d_data, uint64_t* d_out_bytes, uint64_t* d_records_total,
+                                 void* d_scratch, void* hip_stream);
+int32_t rpgpu_legacy_run_device(rpgpu_ctx* ctx, const rpgpu_batch_desc* d_sets, uint32_t nsets,
+                                const uint8_t* d_data, int64_t now_ms, rpgpu_legacy_result* d_lres,
+                                uint8_t* d_out, uint64_t out_cap, rpgpu_batch_desc* d_out_descs,
+                                rpgpu_batch_result* d_out_results, rpgpu_record_index* d_index,
+                                uint64_t index_cap, uint64_t* d_index_used, void* d_scratch, void* hip_stream);
+/* Synchronous scalar mirror (runs on the GPU, host buffers), shaped like
+ * rpgpu_decompress_batch: returns the verdict (>= 0) or a negative status;
+ * verdict OK: `out` holds the on-disk batch, *out_len its bytes;
+ * RPGPU_V_DECOMP_OVERFLOW: *out_len = the capacity needed. */
+int32_t rpgpu_convert_message_set(rpgpu_ctx* ctx, const void* in, size_t n, int64_t now_ms, void* out,
+                                  size_t cap, size_t* out_len);
+/* The error code produce_handler answers for the partition (produce.cc:440-489):
+ * NULL_RECORDS and the legacy_error verdicts (LEGACY_MAGIC, _CRC_MISMATCH,
+ * _LZ4_MAGIC0, _NULL_COMPRESSED) invalid_record; the *_THROW verdicts
+ * unknown_server_error; OK the batch_max_bytes rule of rpgpu_kafka_error_code
+ * on out->size_bytes (out: the set's row of d_out_results; may be NULL when
+ * batch_max_bytes is 0); LEGACY_COMPRESSED the sentinel below, outside the
+ * int16 range of Kafka error codes: the reference's answer depends on the
+ * nested set.  Any other verdict: unknown_server_error.  Pure host function. */
+#define RPGPU_LEGACY_ROUTE_TO_REFERENCE 0x10000
+int32_t rpgpu_legacy_kafka_error_code(const rpgpu_legacy_result* r, const rpgpu_batch_result* out,
+                                      uint32_t batch_max_bytes);
+
+/* ---- generic CRC32 (zlib polynomial) over many byte ranges ----------------
+ * The twins of rpgpu_crc32c_ranges_device / rpgpu_crc32c_extend with the
+ * semantics of crc::crc32 (hashing/crc32.h:18-33; zlib's crc32(seed, p, n)). */
+int32_t rpgpu_crc32_ranges_device(rpgpu_ctx* ctx, const uint8_t* d_data, const uint64_t* d_off,
+                                  const uint32_t* d_len, const uint32_t* d_seed, uint32_t n,
+                                  uint32_t* d_crc_out, void* hip_stream);
+int32_t rpgpu_crc32_extend(rpgpu_ctx* ctx, uint32_t crc, const void* p, size_t n, uint32_t* out);
 
 /* ---- segment offset/time index --------------------------------------------
  * Replaces segment_index::maybe_track (storage/segment_index.cc:98-120) +

@@ -59,11 +59,23 @@ V_SKIPPED = 40
 
 VERDICT_NAMES = {v: k for k, v in globals().items() if k.startswith("V_") and isinstance(v, int)}
 
+# legacy MessageSets (rpgpu_legacy_*): kept apart from VERDICT_NAMES, whose
+# verdicts all belong to rpgpu_kafka_error_code
+V_LEGACY_MAGIC = 50
+V_LEGACY_CRC_MISMATCH = 51
+V_LEGACY_LZ4_MAGIC0 = 52
+V_LEGACY_NULL_COMPRESSED = 53
+V_LEGACY_TRUNC_THROW = 54
+V_LEGACY_BAD_CODEC_THROW = 55
+V_LEGACY_COMPRESSED = 56
+LEGACY_VERDICT_NAMES = {v: k for k, v in globals().items() if k.startswith("V_LEGACY_") and isinstance(v, int)}
+LEGACY_ROUTE_TO_REFERENCE = 0x10000  # rpgpu_legacy_kafka_error_code for V_LEGACY_COMPRESSED
+
 RPGPU_OK = 0
 RPGPU_PENDING = 1
 RPGPU_EINVAL = -1
 RPGPU_ECAPACITY = -4
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 DESC_NULL_RECORDS = 1  # rpgpu_batch_desc.flags
 
@@ -97,6 +109,10 @@ SET_RESULT_DTYPE = np.dtype([("verdict", "<i4"), ("batch_count", "<u4"), ("first
                              ("failed_batch", "<u4")])
 assert DESC_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 64 and DECOMP_RESULT_DTYPE.itemsize == 32
 assert SET_RESULT_DTYPE.itemsize == 16
+LEGACY_RESULT_DTYPE = np.dtype([("verdict", "<i4"), ("record_count", "<i4"), ("event_message", "<i4"),
+                                ("codec", "<u4"), ("timestamp", "<i8"), ("out_offset", "<u8"),
+                                ("out_len", "<u8"), ("out_cap", "<u8")])
+assert LEGACY_RESULT_DTYPE.itemsize == 48
 SEGMENT_DTYPE = np.dtype([("first_batch", "<u4"), ("batch_count", "<u4"), ("base_offset", "<i8"),
                           ("file_base", "<u8"), ("step", "<u4"), ("internal_topic", "u1"),
                           ("with_offset", "u1"), ("reserved", "<u2")])
@@ -270,6 +286,15 @@ def lib() -> C.CDLL:
         _sig(L.rpgpu_record_sets_plan_device, _i32, _vp, _vp, _u32, _vp, _vp, _vp, _vp)
         _sig(L.rpgpu_record_sets_run_device, _i32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u64,
              _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_crc32_ranges_device, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp)
+        _sig(L.rpgpu_crc32_extend, _i32, _vp, _u32, _vp, C.c_size_t, C.POINTER(_u32))
+        _sig(L.rpgpu_legacy_scratch_bytes, C.c_size_t, _u32)
+        _sig(L.rpgpu_legacy_plan_device, _i32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_legacy_run_device, _i32, _vp, _vp, _u32, _vp, C.c_int64, _vp, _vp, _u64, _vp, _vp, _vp,
+             _u64, _vp, _vp, _vp)
+        _sig(L.rpgpu_convert_message_set, _i32, _vp, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t,
+             C.POINTER(C.c_size_t))
+        _sig(L.rpgpu_legacy_kafka_error_code, _i32, _vp, _vp, _u32)
         _LIB = L
     return _LIB
 
@@ -305,4 +330,6 @@ EXPORTED = [
     "rpgpu_uncompress", "rpgpu_decompress_batch", "rpgpu_record_sets_scratch_bytes", "rpgpu_record_sets_plan_device",
     "rpgpu_record_sets_run_device", "rpgpu_segment_index_device",
     "rpgpu_set_max_timestamp", "rpgpu_set_max_timestamp_device",
+    "rpgpu_crc32_ranges_device", "rpgpu_crc32_extend", "rpgpu_legacy_scratch_bytes", "rpgpu_legacy_plan_device",
+    "rpgpu_legacy_run_device", "rpgpu_convert_message_set", "rpgpu_legacy_kafka_error_code",
 ]

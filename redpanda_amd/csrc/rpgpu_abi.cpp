@@ -106,6 +106,14 @@ hipError_t launch_set_max_timestamp(const rpgpu_batch_desc* d_descs, uint32_t n,
 hipError_t launch_kafka_serialize(const uint8_t* d_data, const rpgpu_batch_desc* d_descs, const int64_t* d_terms,
                                   uint32_t n, uint8_t* d_out, const rpgpu_fetch_range* d_ranges, uint32_t nranges,
                                   rpgpu_fetch_summary* d_sums, hipStream_t s);
+size_t legacy_scratch_bytes(uint32_t n);
+hipError_t launch_legacy_plan(const rpgpu_batch_desc* d_sets, uint32_t n, const uint8_t* d_data,
+                              uint64_t* d_out_bytes, uint64_t* d_records_total, void* d_scratch, hipStream_t s);
+hipError_t launch_legacy_run(const rpgpu_batch_desc* d_sets, uint32_t n, const uint8_t* d_data, int64_t now_ms,
+                             rpgpu_legacy_result* d_lres, uint8_t* d_out, uint64_t out_cap,
+                             rpgpu_batch_desc* d_out_descs, rpgpu_batch_result* d_vres2, rpgpu_record_index* d_index,
+                             uint64_t index_cap, uint64_t* d_index_used, void* d_scratch, const uint32_t* d_tables,
+                             const uint32_t* d_tables32, int grid, uint32_t lane_max, hipStream_t s);
 }  // namespace rpgpu
 
 namespace {
@@ -154,6 +162,11 @@ struct rpgpu_ctx {
     rpgpu::DecompStreams dstreams{};  // large-batch wave decoders beside the lane decoders
     bool have_dstreams = false;
     uint32_t* d_tables = nullptr;
+    uint32_t* d_tables32 = nullptr;  // the CRC32 (zlib polynomial) blob of the legacy MessageSet path
+    // legacy MessageSets: CRC ranges up to this many bytes are checksummed by a lane
+    // each, longer ones by a wave each: on 1 GiB arenas the lane path measured faster at
+    // 138 and 438-byte ranges, the wave path at 1,058 and 4,034 bytes
+    uint32_t legacy_lane_max = 512;
     int64_t* d_sum_partial = nullptr;  // partition summaries: per-workgroup tables
     DevBuf work;     // submissions: descs | data | results | index | scratch | used
     DevBuf small;    // scalar mirrors
@@ -283,6 +296,20 @@ rpgpu_ctx* rpgpu_open(int device, const rpgpu_opts* opts) {
         rpgpu_close(c);
         return nullptr;
     }
+    std::vector<uint32_t> t32(rpgpu::kTableWords32);
+    rpgpu::build_tables_crc32(t32.data());
+    if (hipMalloc(&c->d_tables32, sizeof(uint32_t) * t32.size()) != hipSuccess ||
+        hipMemcpy(c->d_tables32, t32.data(), sizeof(uint32_t) * t32.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        rpgpu_close(c);
+        return nullptr;
+    }
+    // diagnostics (scripts/legacy_bench.py --lane-crc): the crossover in bytes;
+    // anything but a whole decimal number is ignored
+    if (const char* lm = getenv("RPGPU_LEGACY_LANE_CRC")) {
+        char* end = nullptr;
+        const unsigned long v = strtoul(lm, &end, 10);
+        if (end != lm && *end == 0 && v <= 0xffffffffull) c->legacy_lane_max = (uint32_t)v;
+    }
     // not fatal: without it the summaries take the global-atomic path
     if (hipMalloc(&c->d_sum_partial, rpgpu::summary_scratch_bytes(c->cu_count)) != hipSuccess)
         c->d_sum_partial = nullptr;
@@ -302,6 +329,7 @@ void rpgpu_close(rpgpu_ctx* c) {
     c->small.release();
     c->small_out.release();
     if (c->d_tables) (void)hipFree(c->d_tables);
+    if (c->d_tables32) (void)hipFree(c->d_tables32);
     if (c->d_sum_partial) (void)hipFree(c->d_sum_partial);
     if (c->overlap.aux) {
         (void)hipStreamSynchronize(c->overlap.aux);
@@ -669,6 +697,63 @@ int32_t rpgpu_crc32c_ranges_device(rpgpu_ctx* c, const uint8_t* d_data, const ui
     return RPGPU_OK;
 }
 
+int32_t rpgpu_crc32_ranges_device(rpgpu_ctx* c, const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len,
+                                  const uint32_t* d_seed, uint32_t n, uint32_t* d_crc_out, void* hip_stream) {
+    if (!c || (n && (!d_data || !d_off || !d_len || !d_crc_out))) return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    // the strided-row kernel of the CRC32C entry point over the zlib polynomial's tables
+    hipError_t e = rpgpu::launch_crc_ranges(d_data, d_off, d_len, d_seed, n, d_crc_out, c->d_tables32, c->grid, s);
+    if (e != hipSuccess) return fail(c, e, "crc32 launch");
+    return RPGPU_OK;
+}
+
+size_t rpgpu_legacy_scratch_bytes(uint32_t n) { return rpgpu::legacy_scratch_bytes(n); }
+
+int32_t rpgpu_legacy_plan_device(rpgpu_ctx* c, const rpgpu_batch_desc* d_sets, uint32_t n, const uint8_t* d_data,
+                                 uint64_t* d_out_bytes, uint64_t* d_records_total, void* d_scratch,
+                                 void* hip_stream) {
+    if (!c || (n && (!d_sets || !d_data || !d_scratch))) return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_legacy_plan(d_sets, n, d_data, d_out_bytes, d_records_total, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "legacy plan launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_legacy_run_device(rpgpu_ctx* c, const rpgpu_batch_desc* d_sets, uint32_t n, const uint8_t* d_data,
+                                int64_t now_ms, rpgpu_legacy_result* d_lres, uint8_t* d_out, uint64_t out_cap,
+                                rpgpu_batch_desc* d_out_descs, rpgpu_batch_result* d_out_results,
+                                rpgpu_record_index* d_index, uint64_t index_cap, uint64_t* d_index_used,
+                                void* d_scratch, void* hip_stream) {
+    if (!c || (n && (!d_sets || !d_data || !d_lres || !d_out || !d_out_descs || !d_out_results || !d_scratch)) ||
+        (reinterpret_cast<uintptr_t>(d_out) & 15u))  // the message table in d_out is read as 16-byte words
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_legacy_run(d_sets, n, d_data, now_ms, d_lres, d_out, out_cap, d_out_descs,
+                                            d_out_results, d_index, d_index ? index_cap : 0, d_index_used, d_scratch,
+                                            c->d_tables, c->d_tables32, c->grid, c->legacy_lane_max, s);
+    if (e != hipSuccess) return fail(c, e, "legacy run launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_legacy_kafka_error_code(const rpgpu_legacy_result* r, const rpgpu_batch_result* out,
+                                      uint32_t batch_max_bytes) {
+    if (!r) return RPGPU_KAFKA_ERR_UNKNOWN_SERVER_ERROR;
+    switch (r->verdict) {
+    case RPGPU_V_NULL_RECORDS:            // !part.records (produce.cc:440-449)
+    case RPGPU_V_LEGACY_MAGIC:            // adapter.legacy_error (produce.cc:451-460)
+    case RPGPU_V_LEGACY_CRC_MISMATCH:
+    case RPGPU_V_LEGACY_LZ4_MAGIC0:
+    case RPGPU_V_LEGACY_NULL_COMPRESSED:
+        return RPGPU_KAFKA_ERR_INVALID_RECORD;
+    case RPGPU_V_LEGACY_COMPRESSED:       // the nested set decides: not guessed here
+        return RPGPU_LEGACY_ROUTE_TO_REFERENCE;
+    case RPGPU_V_OK:                      // valid_crc and v2_format are set by the adapter
+        return rpgpu::kafka_error_code(RPGPU_V_OK, out ? out->size_bytes : 0, out ? batch_max_bytes : 0);
+    default:                              // an exception escapes the request decoder
+        return RPGPU_KAFKA_ERR_UNKNOWN_SERVER_ERROR;
+    }
+}
+
 int32_t rpgpu_submit(rpgpu_ctx* c, const rpgpu_batch_desc* descs, uint32_t n, const void* data,
                      size_t data_len, rpgpu_batch_result* out_results, rpgpu_record_index* out_index,
                      uint64_t index_cap, uint64_t* out_index_used, rpgpu_ticket* ticket) {
@@ -796,7 +881,7 @@ int32_t rpgpu_sync(rpgpu_ctx* c) {
 }
 
 // ---- synchronous scalar mirrors ------------------------------------------
-static int32_t crc_one(rpgpu_ctx* c, uint32_t seed, const void* p, size_t n, uint32_t* out) {
+static int32_t crc_one(rpgpu_ctx* c, const uint32_t* d_tables, uint32_t seed, const void* p, size_t n, uint32_t* out) {
     (void)hipSetDevice(c->device);
     const size_t o_data = 0;
     const size_t o_meta = align_up(n + 16, 256);
@@ -814,7 +899,7 @@ static int32_t crc_one(rpgpu_ctx* c, uint32_t seed, const void* p, size_t n, uin
     e = rpgpu::launch_crc_ranges(base, reinterpret_cast<uint64_t*>(base + o_meta),
                                  reinterpret_cast<uint32_t*>(base + o_meta + 8),
                                  reinterpret_cast<uint32_t*>(base + o_meta + 12), 1,
-                                 reinterpret_cast<uint32_t*>(base + o_meta + 16), c->d_tables, 1, c->stream);
+                                 reinterpret_cast<uint32_t*>(base + o_meta + 16), d_tables, 1, c->stream);
     if (e != hipSuccess) return fail(c, e, "crc launch");
     if ((e = hipMemcpyAsync(out, base + o_meta + 16, 4, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
         (e = hipStreamSynchronize(c->stream)) != hipSuccess)
@@ -933,7 +1018,68 @@ int32_t rpgpu_decompress_batch(rpgpu_ctx* c, const void* batch, size_t len, int3
 
 int32_t rpgpu_crc32c_extend(rpgpu_ctx* c, uint32_t crc, const void* p, size_t n, uint32_t* out) {
     if (!c || !out || (n && !p) || n > 0xffffffffu) return RPGPU_EINVAL;
-    return crc_one(c, crc, p, n, out);
+    return crc_one(c, c->d_tables, crc, p, n, out);
+}
+
+int32_t rpgpu_crc32_extend(rpgpu_ctx* c, uint32_t crc, const void* p, size_t n, uint32_t* out) {
+    if (!c || !out || (n && !p) || n > 0xffffffffu) return RPGPU_EINVAL;
+    return crc_one(c, c->d_tables32, crc, p, n, out);
+}
+
+// kafka_batch_adapter::adapt_with_version (version < 3) for one set: the arena
+// path with one descriptor, then the batch copied back
+int32_t rpgpu_convert_message_set(rpgpu_ctx* c, const void* in, size_t n, int64_t now_ms, void* out, size_t cap,
+                                  size_t* out_len) {
+    if (!c || (n && !in) || !out_len || (cap && !out) || n > 0x7fffffffu) return RPGPU_EINVAL;
+    *out_len = 0;
+    (void)hipSetDevice(c->device);
+    // small: data + pad | desc | totals (out bytes, records) | lres | out desc | out result | used | scratch
+    const size_t o_desc = align_up(n + RPGPU_ARENA_TAIL_PAD, 256);
+    const size_t o_tot = o_desc + 64, o_lres = o_tot + 64, o_od = o_lres + 64, o_or = o_od + 64, o_used = o_or + 64;
+    const size_t o_scr = align_up(o_used + 64, 256);
+    hipError_t e = c->small.reserve(o_scr + rpgpu::legacy_scratch_bytes(1));
+    if (e != hipSuccess) return fail(c, e, "device buffer");
+    uint8_t* base = static_cast<uint8_t*>(c->small.p);
+    rpgpu_batch_desc d;
+    memset(&d, 0, sizeof(d));
+    d.length = (uint32_t)n;
+    d.format = RPGPU_FMT_KAFKA_WIRE;
+    d.ops = RPGPU_OPS_PRODUCE;
+    if ((n && (e = hipMemcpyAsync(base, in, n, hipMemcpyHostToDevice, c->stream)) != hipSuccess) ||
+        (e = hipMemsetAsync(base + n, 0, RPGPU_ARENA_TAIL_PAD, c->stream)) != hipSuccess ||
+        (e = hipMemcpyAsync(base + o_desc, &d, sizeof(d), hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+        return fail(c, e, "upload");
+    const rpgpu_batch_desc* d_set = reinterpret_cast<const rpgpu_batch_desc*>(base + o_desc);
+    uint64_t* d_tot = reinterpret_cast<uint64_t*>(base + o_tot);
+    if ((e = rpgpu::launch_legacy_plan(d_set, 1, base, d_tot, d_tot + 1, base + o_scr, c->stream)) != hipSuccess)
+        return fail(c, e, "legacy plan launch");
+    uint64_t tot[2] = {0, 0};
+    if ((e = hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+        return fail(c, e, "download");
+    const size_t out_cap = tot[0] + RPGPU_ARENA_TAIL_PAD;
+    const size_t o_index = align_up(out_cap, 256);
+    if ((e = c->small_out.reserve(o_index + (tot[1] + 1) * sizeof(rpgpu_record_index))) != hipSuccess)
+        return fail(c, e, "device buffer");
+    uint8_t* dout = static_cast<uint8_t*>(c->small_out.p);
+    e = rpgpu::launch_legacy_run(d_set, 1, base, now_ms, reinterpret_cast<rpgpu_legacy_result*>(base + o_lres), dout,
+                                 out_cap, reinterpret_cast<rpgpu_batch_desc*>(base + o_od),
+                                 reinterpret_cast<rpgpu_batch_result*>(base + o_or),
+                                 reinterpret_cast<rpgpu_record_index*>(dout + o_index), tot[1] + 1,
+                                 reinterpret_cast<uint64_t*>(base + o_used), base + o_scr, c->d_tables, c->d_tables32,
+                                 c->grid, c->legacy_lane_max, c->stream);
+    if (e != hipSuccess) return fail(c, e, "legacy run launch");
+    rpgpu_legacy_result r;
+    if ((e = hipMemcpyAsync(&r, base + o_lres, sizeof(r), hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+        return fail(c, e, "download");
+    if (r.verdict != RPGPU_V_OK) return r.verdict;
+    *out_len = r.out_len;
+    if (r.out_len > cap) return RPGPU_V_DECOMP_OVERFLOW;
+    if ((e = hipMemcpyAsync(out, dout + r.out_offset, r.out_len, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(c->stream)) != hipSuccess)
+        return fail(c, e, "download");
+    return RPGPU_V_OK;
 }
 
 int32_t rpgpu_internal_header_only_crc(rpgpu_ctx* c, const rpgpu_rp_header* h, uint32_t* out) {

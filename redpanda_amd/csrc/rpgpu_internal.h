@@ -29,6 +29,12 @@ constexpr int kOffU = kOffT0 + 256;      // kRowsPerChunk x 8 x 16: x^(-8*1024*m
 constexpr int kOffHB = kOffU + kRowsPerChunk * 128;
 constexpr int kTableWords = kOffHB + 2 * 16 * 64;
 static_assert(kTableWords % 4 == 0, "table blob is copied as 16-byte words");
+// The CRC32 (zlib polynomial) blob of the legacy MessageSet kernels: the same
+// layout, then the one-lane-per-range tables (rpgpu_tables.cpp).
+constexpr int kOffB = kTableWords;        // 32 x 16: block nibble tables, not pre-shifted
+constexpr int kOffL1 = kOffB + 32 * 16;   // 2 x 16: the byte table by nibbles
+constexpr int kTableWords32 = kOffL1 + 32;
+static_assert(kTableWords32 % 4 == 0, "table blob is copied as 16-byte words");
 
 constexpr int kValidateThreads = 256;  // 4 waves per workgroup
 constexpr int kWavesPerBlock = kValidateThreads / 64;
@@ -57,6 +63,7 @@ struct DecompStreams {
 };
 
 void build_tables(uint32_t* out /* kTableWords */);
+void build_tables_crc32(uint32_t* out /* kTableWords32 */);
 
 // Produce-handler verdict -> Kafka error code (produce.cc:440-489 in its
 // order: null records, legacy error, !valid_crc, !v2_format || !batch; then

@@ -699,57 +699,11 @@ __global__ __launch_bounds__(kValidateThreads) void crc_ranges_kernel(
     const uint32_t wave = threadIdx.x >> 6;
     const uint32_t gw = __builtin_amdgcn_readfirstlane(blockIdx.x * kWavesPerBlock + wave);
     const uint32_t nw = gridDim.x * kWavesPerBlock;
-    const uint32_t* sV = sT + kOffN;
     for (uint32_t i = gw; i < n; i += nw) {
         const uint8_t* base = data + offs[i];
         const int64_t len = lens[i];
         const uint32_t init = ~(seeds ? seeds[i] : 0u);
-        uint32_t crc;
-        if (len < 4) {
-            uint32_t s = init;
-            for (int64_t k = 0; k < len; k++) s = sT[kOffT0 + ((s ^ base[k]) & 255)] ^ (s >> 8);
-            crc = ~s;
-        } else {
-            const int64_t nblocks = (len + 15) >> 4;
-            const int64_t niter = (nblocks + 63) >> 6;
-            const int64_t g0 = len - (niter << 10);
-            uint32_t c = 0;
-            for (int64_t it = 0; it < niter; it++) {
-                const int64_t ro = g0 + (it << 10) + 16 * (int64_t)l;
-                u32x4 x = {0, 0, 0, 0};
-                if (ro + 16 > 0) {
-                    if (ro >= 0) {
-                        x = ld16(base + ro);
-                    } else {
-                        // straddles the range start: assemble from bytes >= 0
-                        uint32_t wv[4] = {0, 0, 0, 0};
-                        for (int k = 0; k < 16; k++)
-                            if (ro + k >= 0) wv[k >> 2] |= (uint32_t)base[ro + k] << (8 * (k & 3));
-                        x = (u32x4){wv[0], wv[1], wv[2], wv[3]};
-                    }
-                    if (ro < 4) {
-#pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            const int64_t o4 = ro + 4 * q;
-                            uint32_t m = 0;
-#pragma unroll
-                            for (int j = 0; j < 4; j++) {
-                                const int64_t o = o4 + j;
-                                if (o >= 0 && o < 4) m |= ((init >> (8 * o)) & 255u) << (8 * j);
-                            }
-                            if (q == 0) x.x ^= m;
-                            if (q == 1) x.y ^= m;
-                            if (q == 2) x.z ^= m;
-                            if (q == 3) x.w ^= m;
-                        }
-                    }
-                }
-                x.x ^= c;
-                c = crc_block(sV, x);
-            }
-            c = combine64(sT + kOffW, c);
-            crc = ~rdl(c, 0);
-        }
+        const uint32_t crc = crc_range_wave(sT, base, len, init, l);
         if (l == 0) out[i] = crc;
     }
 }

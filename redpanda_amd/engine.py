@@ -134,6 +134,62 @@ class Engine:
         if rc != abi.RPGPU_OK:
             raise EngineError(f"rpgpu_crc32c_ranges_device: {rc} {self.last_error()}")
 
+    def crc32_ranges_device(self, d_data: int, d_off: int, d_len: int, d_seed: int, n: int,
+                            d_out: int, stream: int = 0) -> None:
+        """rpgpu_crc32_ranges_device: zlib crc32 (crc::crc32) over many ranges."""
+        rc = self._lib.rpgpu_crc32_ranges_device(self._ctx, d_data, d_off, d_len, d_seed or None,
+                                                 n, d_out, _stream(stream))
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_crc32_ranges_device: {rc} {self.last_error()}")
+
+    # -- legacy MessageSets (rpgpu_legacy_plan_device / rpgpu_legacy_run_device) --------
+    def convert_legacy_sets(self, data: np.ndarray, sets: np.ndarray, now_ms: int, runs: int = 1) -> dict:
+        """kafka_batch_adapter::adapt_with_version for produce versions below 3
+        over many record sets (device entry points, HBM from torch).  Returns
+        host copies: lres (per-set outcome), out (output buffer), out_descs,
+        out_results, index, used, out_bytes, records_total."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        sets = np.ascontiguousarray(sets, dtype=abi.DESC_DTYPE)
+        n = len(sets)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        m = max(n, 1)
+        d_data = torch.from_numpy(data.copy()).to(dev)
+        d_sets = torch.from_numpy(sets.view(np.uint8).copy()).to(dev)
+        d_tot = torch.zeros(3, dtype=torch.int64, device=dev)
+        d_scr = torch.zeros(max(int(self._lib.rpgpu_legacy_scratch_bytes(n)), 1), dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_legacy_plan_device(self._ctx, d_sets.data_ptr(), n, d_data.data_ptr(), d_tot.data_ptr(),
+                                                d_tot.data_ptr() + 8, d_scr.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_legacy_plan_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        out_bytes, records_total = int(d_tot[0].item()), int(d_tot[1].item())
+        out_cap = out_bytes + abi.ARENA_TAIL_PAD
+        index_cap = records_total + 1
+        d_out = torch.zeros(out_cap, dtype=torch.uint8, device=dev)
+        d_lres = torch.zeros(m * 48, dtype=torch.uint8, device=dev)
+        d_odescs = torch.zeros(m * 24, dtype=torch.uint8, device=dev)
+        d_ores = torch.zeros(m * 64, dtype=torch.uint8, device=dev)
+        d_index = torch.zeros(index_cap * 32, dtype=torch.uint8, device=dev)
+        for _ in range(runs):  # a plan may be run any number of times
+            rc = self._lib.rpgpu_legacy_run_device(self._ctx, d_sets.data_ptr(), n, d_data.data_ptr(), now_ms,
+                                                   d_lres.data_ptr(), d_out.data_ptr(), out_cap, d_odescs.data_ptr(),
+                                                   d_ores.data_ptr(), d_index.data_ptr(), index_cap,
+                                                   d_tot.data_ptr() + 16, d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_legacy_run_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        used = int(d_tot[2].item())
+        return dict(
+            lres=d_lres.cpu().numpy().view(abi.LEGACY_RESULT_DTYPE)[:n].copy(),
+            out=d_out.cpu().numpy(),
+            out_descs=d_odescs.cpu().numpy().view(abi.DESC_DTYPE)[:n].copy(),
+            out_results=d_ores.cpu().numpy().view(abi.RESULT_DTYPE)[:n].copy(),
+            index=d_index.cpu().numpy().view(abi.INDEX_DTYPE)[: min(used, index_cap)].copy(),
+            used=used, out_bytes=out_bytes, records_total=records_total)
+
     # -- decompression (rpgpu_decomp_plan_device / rpgpu_decomp_run_device) -------------
     def decomp_scratch_bytes(self, n: int) -> int:
         """rpgpu_decomp_scratch_bytes_ctx: the scratch this context's decompress calls need."""
@@ -573,6 +629,31 @@ class Engine:
         if v < 0:
             raise EngineError(f"rpgpu_decompress_batch: {v} {self.last_error()}")
         return int(v), out[: min(n.value, cap)].tobytes(), int(n.value)
+
+    def convert_message_set(self, data: bytes | np.ndarray, now_ms: int, cap: int | None = None) -> tuple[int, bytes, int]:
+        """rpgpu_convert_message_set: one legacy MessageSet to its v2 on-disk
+        batch.  Returns (verdict, batch, out_len)."""
+        a = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))
+        cap = cap if cap is not None else a.size + abi.HEADER_SIZE
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        n = C.c_size_t()
+        v = self._lib.rpgpu_convert_message_set(self._ctx, a.ctypes.data if a.size else None, a.size, now_ms,
+                                                out.ctypes.data, cap, C.byref(n))
+        if v < 0:
+            raise EngineError(f"rpgpu_convert_message_set: {v} {self.last_error()}")
+        return int(v), out[: min(n.value, cap)].tobytes() if v == abi.V_OK else b"", int(n.value)
+
+    def crc32_extend(self, crc: int, data: bytes | np.ndarray) -> int:
+        """crc::crc32 (zlib's crc32(crc, data)) on the GPU."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        out = C.c_uint32()
+        rc = self._lib.rpgpu_crc32_extend(self._ctx, crc & 0xFFFFFFFF, buf.ctypes.data if buf.size else None,
+                                          buf.size, C.byref(out))
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_crc32_extend: {rc} {self.last_error()}")
+        return int(out.value)
+
     def crc32c_extend(self, crc: int, data: bytes | np.ndarray) -> int:
         buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else data
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
@@ -680,6 +761,16 @@ class Engine:
     def kafka_error_code(result: np.ndarray, batch_max_bytes: int = 0) -> int:
         r = np.ascontiguousarray(result, dtype=abi.RESULT_DTYPE).reshape(1)
         return int(abi.lib().rpgpu_kafka_error_code(r.ctypes.data, batch_max_bytes))
+
+    @staticmethod
+    def legacy_kafka_error_code(lres: np.ndarray, out_result: np.ndarray | None = None,
+                                batch_max_bytes: int = 0) -> int:
+        """rpgpu_legacy_kafka_error_code for one set's result row (and its row
+        of out_results, needed for the batch_max_bytes rule)."""
+        r = np.ascontiguousarray(lres, dtype=abi.LEGACY_RESULT_DTYPE).reshape(1)
+        o = None if out_result is None else np.ascontiguousarray(out_result, dtype=abi.RESULT_DTYPE).reshape(1)
+        return int(abi.lib().rpgpu_legacy_kafka_error_code(r.ctypes.data, None if o is None else o.ctypes.data,
+                                                           batch_max_bytes))
 
 
 # ---- workload construction (librpgen.so) -----------------------------------------
