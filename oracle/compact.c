@@ -308,6 +308,7 @@ uint64_t orc_compact_rewrite(const uint8_t* data, const rpgpu_batch_desc* descs,
         rpgpu_compact_result* c = &cres[b];
         memset(c, 0, sizeof(*c));
         memset(&odescs[b], 0, sizeof(odescs[b]));
+        odescs[b].offset = at; /* also without an output (length 0, ops 0), as orc_decompress_batches */
         odescs[b].partition = d->partition;
         odescs[b].format = RPGPU_FMT_RP_DISK;
         c->action = RPGPU_COMPACT_SKIPPED;
@@ -389,7 +390,6 @@ uint64_t orc_compact_rewrite(const uint8_t* data, const rpgpu_batch_desc* descs,
             h.header_crc = orc_internal_header_only_crc(&h);
             memcpy(o, &h, RPGPU_HEADER_SIZE);
         }
-        odescs[b].offset = at;
         odescs[b].length = (uint32_t)c->out_len;
         odescs[b].ops = (uint8_t)(RPGPU_OP_CRC | RPGPU_OP_HDRCRC | (d->ops & (RPGPU_OP_PARSE | RPGPU_OP_INDEX)));
         at += (c->out_len + 15) & ~(uint64_t)15;

@@ -90,6 +90,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t h) {  // splitmix64 finaliser
     h ^= h >> 31;
     return h;
 }
+// restated by tests/compaction_geometry.py (mix64 / key_hash / set_hash, behind wrap_keys): change both
 __device__ __forceinline__ uint64_t key_hash(const uint8_t* k, uint32_t len, uint32_t scope, uint8_t type) {
     uint64_t h = mix64(((uint64_t)scope << 32) ^ ((uint64_t)type << 24) ^ len ^ 0x9e3779b97f4a7c15ull);
     uint32_t i = 0;

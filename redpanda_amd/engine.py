@@ -448,10 +448,15 @@ class Engine:
 
     # -- compaction rewrite (rpgpu_compaction_rewrite_plan_device / run_device) ------------
     def compaction_rewrite(self, data: np.ndarray, descs: np.ndarray, results: np.ndarray, index: np.ndarray,
-                           keep: np.ndarray) -> dict:
+                           keep: np.ndarray, out_cap: int | None = None, alloc: int | None = None) -> dict:
         """copy_data_segment_reducer::filter over a validated, indexed arena and
         its keep flags, on the GPU.  Returns host copies: cres, out, out_descs,
-        out_results, index, used, out_bytes."""
+        out_results, index, used, out_bytes.  out_cap: the output capacity the
+        run is told (default: the planned bytes + ARENA_TAIL_PAD; below the plan,
+        batches whose slot does not fit come back SKIPPED).  alloc: bytes of the
+        output buffer (>= out_cap + ARENA_TAIL_PAD; when given the buffer is
+        pre-filled with 0xA5 and returned whole, so a caller can see that
+        nothing past out_cap was written)."""
         import torch
 
         dev = torch.device("cuda", self.device)
@@ -480,9 +485,15 @@ class Engine:
             raise EngineError(f"rpgpu_compaction_rewrite_plan_device: {rc} {self.last_error()}")
         torch.cuda.synchronize(dev)
         out_bytes = int(d_used[0].item())
-        out_cap = out_bytes + abi.ARENA_TAIL_PAD
+        if out_cap is None:
+            out_cap = out_bytes + abi.ARENA_TAIL_PAD
         index_cap = int(np.maximum(results["record_count"], 0).astype(np.int64).sum()) + 1
-        d_out = torch.zeros(out_cap, dtype=torch.uint8, device=dev)
+        if alloc is None:
+            d_out = torch.zeros(out_cap, dtype=torch.uint8, device=dev)
+        else:
+            if alloc < out_cap + abi.ARENA_TAIL_PAD:
+                raise ValueError("alloc must be at least out_cap + ARENA_TAIL_PAD")
+            d_out = torch.full((alloc,), 0xA5, dtype=torch.uint8, device=dev)
         d_cres = torch.zeros(m * abi.COMPACT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         d_odescs = torch.zeros(m * 24, dtype=torch.uint8, device=dev)
         d_ores = torch.zeros(m * 64, dtype=torch.uint8, device=dev)

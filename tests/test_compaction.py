@@ -36,7 +36,9 @@ def python_keep(data, descs, res, index):
         r = res[b]
         if r["verdict"] != 0:
             continue
-        lo, hi = int(r["index_first"]), int(r["index_first"]) + int(r["index_count"])
+        lo, hi = int(r["index_first"]), min(int(r["index_first"]) + int(r["index_count"]), len(index))
+        if lo >= len(index):  # a truncated index: the batch is not indexed (compact.c, compact_keys_kernel)
+            continue
         if int(r["type"]) in NON_COMPACTIBLE:
             keep[lo:hi] = 1
             continue
@@ -53,7 +55,7 @@ def python_keep(data, descs, res, index):
         r = res[b]
         if r["verdict"] != 0 or int(r["type"]) in NON_COMPACTIBLE:
             continue
-        for j in range(int(r["index_first"]), int(r["index_first"]) + int(r["index_count"])):
+        for j in range(int(r["index_first"]), min(int(r["index_first"]) + int(r["index_count"]), len(index))):
             keep[j] = 1 if (int(descs["partition"][b]), int(index[j]["offset"])) in kept else 0
     return keep, len(latest)
 
@@ -302,6 +304,11 @@ def _i32(v):
     return v - (1 << 32) if v >> 31 else v
 
 
+def _i64(v):
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
+
+
 def python_filter(body: bytes, rc: int, keep_flags) -> tuple[bytes, int, int]:
     """filter() steps 1 and 4 with append_record_to_buffer (record_utils.cc:
     183-225): (re-encoded kept records, first kept ts delta, last kept ts delta)."""
@@ -409,9 +416,9 @@ def python_rewrite_check(data, descs, res, idx, keep, got):
         h = np.frombuffer(out[:61], dtype=abi.RP_HEADER_DTYPE)[0]
         assert int(h["attrs"]) & 0xFFFF == attrs and int(h["base_offset"]) == int(r["base_offset"])
         if want_action == abi.COMPACT_FILTERED:
-            ft = int(r["first_timestamp"]) + first
+            ft = _i64(int(r["first_timestamp"]) + first)  # int64 arithmetic wraps
             assert int(h["first_timestamp"]) == ft and int(h["record_count"]) == int((k == 1).sum())
-            mt = ft + last if not attrs & 0x08 else int(r["max_timestamp"])  # the reference's max rule
+            mt = _i64(ft + last) if not attrs & 0x08 else int(r["max_timestamp"])  # the reference's max rule
             assert int(h["max_timestamp"]) == mt
         assert int(h["header_crc"]) == orc.internal_header_only_crc(np.frombuffer(out[:61], dtype=abi.RP_HEADER_DTYPE))
         be40 = struct.pack(">hiqqqhii", int(h["attrs"]), int(h["last_offset_delta"]), int(h["first_timestamp"]),
@@ -455,3 +462,153 @@ def test_gpu_compaction_rewrite(eng, fmt):
         assert np.array_equal(got["out_results"][f], want["out_results"][f]), f
     assert got["used"] == want["used"]
     assert np.array_equal(got["index"].view(np.uint8), want["index"].view(np.uint8))
+
+
+# ---- record-geometry arenas (tests/compaction_geometry.py) ------------------------------
+import compaction_geometry as geo  # noqa: E402
+
+GEO_CASES = [(name, fmt) for name in geo.BUILDERS for fmt in (DISK, WIRE)]
+GEO_IDS = [f"{name}-{'disk' if fmt == DISK else 'wire'}" for name, fmt in GEO_CASES]
+
+
+def batch_keep(c, b):
+    lo = int(c["res"]["index_first"][b])
+    return list(c["keep"][lo:lo + int(c["res"]["index_count"][b])])
+
+
+@pytest.mark.parametrize("name,fmt", GEO_CASES, ids=GEO_IDS)
+def test_oracle_geometry_matches_restatements(name, fmt):
+    """The serial oracle against the dict restatement (keep) and python_filter
+    (rewrite) on every geometry arena: a GPU mismatch on one of these arenas then
+    points at the kernel."""
+    c = geo.oracle_chain(name, fmt)
+    want, wkeys = python_keep(c["data"], c["descs"], c["res"], c["idx"])
+    assert np.array_equal(c["keep"], want) and c["nkeys"] == wkeys
+    python_rewrite_check(c["data"], c["descs"], c["res"], c["idx"], c["keep"], c["want"])
+    ok = c["want"]["cres"]["out_len"] > 0
+    assert (c["want"]["out_results"]["verdict"][ok] == abi.V_OK).all()
+    assert (c["want"]["out_results"]["record_count"][ok] == c["want"]["cres"]["record_count"][ok]).all()
+    assert c["data"].size < 1 << 20
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_length_arena_coverage(fmt):
+    c = geo.oracle_chain("length", fmt)
+    n1 = len(geo.LENS)
+    assert (c["res"]["verdict"] == abi.V_OK).all()
+    act = c["want"]["cres"]["action"]
+    for b in range(n1):  # round 1: records 0, 3 and 4 survive
+        assert act[b] == abi.COMPACT_FILTERED and batch_keep(c, b) == [1, 0, 0, 1, 1, 0], b
+    pats = {tuple(batch_keep(c, b)) for b in range(n1, 2 * n1) if act[b] == abi.COMPACT_FILTERED}
+    assert {(1, 0, 0), (0, 0, 1), (1, 0, 1)} <= pats  # first only, last only, all but one
+    for li in range(n1):
+        assert batch_keep(c, n1 + li) == geo.length_round2_keep(li)
+    # key, value and header ranges of one length start at different misalignments
+    for b in range(n1):
+        lo = int(c["res"]["index_first"][b])
+        e = c["idx"][lo:lo + 6]
+        assert len({int(x) % 16 for x in e["key_off"]} | {int(x) % 16 for x in e["val_off"]}) >= 4
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_count_arena_coverage(fmt):
+    c = geo.oracle_chain("count", fmt)
+    assert (c["res"]["verdict"] == abi.V_OK).all()
+    assert list(c["res"]["record_count"][:len(geo.COUNTS)]) == geo.COUNTS
+    act = {cnt: int(c["want"]["cres"]["action"][b]) for b, cnt in enumerate(geo.COUNTS)}
+    assert act[geo.DROPPED_COUNT] == abi.COMPACT_DROPPED and act[geo.KEPT_COUNT] == abi.COMPACT_KEPT
+    for cnt in (63, 127, 129, geo.FIRST_TRIP_COUNT, geo.LATER_TRIPS_COUNT):
+        assert act[cnt] == abi.COMPACT_FILTERED
+    assert batch_keep(c, geo.COUNTS.index(geo.FIRST_TRIP_COUNT)) == [1] * 64 + [0] * 64
+    assert batch_keep(c, geo.COUNTS.index(geo.LATER_TRIPS_COUNT)) == [0] * 64 + [1] * 136
+    assert batch_keep(c, geo.COUNTS.index(129)) == [0] * 119 + [1] * 10
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_key_edge_arena_coverage(fmt):
+    """The verdicts the arena exists for, spelled out (not only oracle == restatement)."""
+    c = geo.oracle_chain("key_edge", fmt)
+    assert (c["res"]["verdict"] == abi.V_OK).all()
+    # batch 0: of each last-byte pair one is superseded, of each prefix chain the middle one, null == empty
+    assert batch_keep(c, 0) == [0, 1, 1, 0, 0, 1, 1, 0] + [1, 0, 1, 1, 0, 1] + [0, 0]
+    assert batch_keep(c, 2) == [1 if fmt == DISK else 0, 1]  # batch types 1 and 5: two keys on disk only
+    assert batch_keep(c, 3) == [1] and batch_keep(c, 4) == [1]  # two scopes: two keys
+    assert batch_keep(c, 7) == [1] and batch_keep(c, 8) == [1]  # the duplicate-offset rule keeps the old "dup-z"
+    for k, base in enumerate(geo.EDGE_BASES):
+        b = 9 + 2 * k
+        assert int(c["res"]["base_offset"][b]) == base
+        assert batch_keep(c, b) == [0, 0, 1] and batch_keep(c, b + 1) == [1, 1]
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_many_batches_arena_coverage(fmt):
+    c = geo.oracle_chain("many_batches", fmt)
+    cres = c["want"]["cres"]
+    seen = set(int(a) for a in cres["action"])
+    want = {abi.COMPACT_SKIPPED, abi.COMPACT_DROPPED, abi.COMPACT_KEPT, abi.COMPACT_TX_CLEARED,
+            abi.COMPACT_FILTERED}
+    if fmt == DISK:  # a wire batch has no type field: it is always raft_data, never non-compactible
+        want.add(abi.COMPACT_NOT_COMPACTIBLE)
+    assert seen == want
+    assert len(cres) == 2600 and int((cres["out_len"] > 0).sum()) > 2048
+    for b in (1023, 1024, 2047):
+        assert cres["action"][b] == abi.COMPACT_SKIPPED and cres["out_len"][b] == 0
+    for b in (1022, 1025, 2046, 2048):  # their neighbours across the scan blocks' edges have slots
+        assert cres["out_len"][b] > 0
+    assert int(cres["out_offset"][geo.SHORT_CAP_BATCH]) > 0
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_table_arenas_coverage(fmt):
+    cap = geo.WRAP_CAP
+    keys = geo.wrap_keys(cap, 0, 1, geo.WRAP_KEYS)
+    assert len(set(keys)) == geo.WRAP_KEYS and all(len(k) == 8 for k in keys)
+    assert all(geo.key_hash(k, 0, 1) & (cap - 1) == cap - 1 for k in keys)
+    c = geo.oracle_chain("wrap", fmt)
+    assert (c["res"]["verdict"] == abi.V_OK).all()
+    assert len(c["idx"]) == geo.WRAP_RECORDS and 2 * len(c["idx"]) == cap
+    assert c["nkeys"] == geo.WRAP_RECORDS - geo.WRAP_KEYS
+    # the four keys are the first records of both batches; their latest offsets wrap the keep set too
+    d, o0, o1 = c["data"], int(c["descs"]["offset"][0]), int(c["descs"]["offset"][1])
+    for j, k in enumerate(keys):
+        for o, e in ((o0, c["idx"][j]), (o1, c["idx"][16 + j])):
+            assert d[o + int(e["key_off"]):o + int(e["key_off"]) + 8].tobytes() == k
+        assert geo.set_hash(0, int(c["idx"]["offset"][16 + j])) & (cap - 1) == cap - 1
+    assert batch_keep(c, 0) == [0] * 4 + [1] * 12 and batch_keep(c, 1) == [1] * 16
+    for records in (32, 64, 1024, 4096):
+        c = geo.oracle_chain(f"full_load_{records}", fmt)
+        assert len(c["idx"]) == records and c["nkeys"] == records and (c["keep"] == 1).all()
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_varint_arena_coverage(fmt):
+    c = geo.oracle_chain("varint", fmt)
+    hit = 0
+    for b in range(len(c["descs"])):
+        r = c["res"][b]
+        if r["verdict"] != abi.V_OK or c["want"]["cres"]["action"][b] != abi.COMPACT_FILTERED:
+            continue
+        e = c["idx"][int(r["index_first"]) + int(r["index_count"]) - 1]
+        ko = int(c["descs"]["offset"][b]) + int(e["key_off"])
+        if c["data"][ko:ko + len(geo.PAST_END_KEY)].tobytes() == geo.PAST_END_KEY and batch_keep(c, b)[-1] == 1:
+            hit += 1
+    assert hit >= 1
+
+
+@pytest.mark.parametrize("fmt", [DISK, WIRE])
+def test_oracle_truncated_index(fmt):
+    """An index cut in the middle of the 129-record batch: keys up to the cut
+    count, the cut batch and every later one are not rewritten."""
+    c = geo.oracle_chain("count", fmt)
+    b, cut = geo.count_cut(c["res"])
+    idx = c["idx"][:cut]
+    keep, nkeys = orc.compaction_keep(c["data"], c["descs"], c["res"], idx)
+    want, wkeys = python_keep(c["data"], c["descs"], c["res"], idx)
+    assert len(keep) == cut and np.array_equal(keep, want) and nkeys == wkeys
+    lo = int(c["res"]["index_first"][b])
+    assert (keep[lo:] != 2).all() and not np.array_equal(keep, c["keep"][:cut])
+    got = orc.compaction_rewrite(c["data"], c["descs"], c["res"], idx, keep)
+    past = c["res"]["index_first"].astype(np.int64) + c["res"]["index_count"].astype(np.int64) > cut
+    assert past[b] and past[b:].all() and not past[:b].any()
+    assert (got["cres"]["action"][past] == abi.COMPACT_SKIPPED).all() and (got["cres"]["out_len"][past] == 0).all()
+    assert (got["cres"]["action"][~past] != abi.COMPACT_SKIPPED).all()
