@@ -268,10 +268,15 @@ class Engine:
             index=d_index.cpu().numpy().view(abi.INDEX_DTYPE)[: min(used, index_cap)].copy(),
             used=used, out_bytes=out_bytes)
 
-    def compress_arena(self, data: np.ndarray, descs: np.ndarray, codec: int) -> dict:
+    def compress_arena(self, data: np.ndarray, descs: np.ndarray, codec: int, plan_codec: int | None = None,
+                       out_cap: int | None = None, runs: int = 1) -> dict:
         """Validate a host arena, then compress its OK uncompressed batches
         (rpgpu_compress_plan_device / rpgpu_compress_run_device).  Returns host
-        copies: results, cres, out, out_descs, out_results, out_bytes."""
+        copies: results, cres, out, out_descs, out_results, out_bytes.
+        plan_codec: plan the slots for another codec than the run's.  out_cap:
+        the capacity handed to the run instead of the plan's; the buffer is then
+        still plan size + 4 KiB, filled with 0xA5, so a write past out_cap shows.
+        runs: run that many times on the one plan and scratch."""
         import torch
 
         dev = torch.device("cuda", self.device)
@@ -290,22 +295,32 @@ class Engine:
         self.validate_device(d_descs.data_ptr(), n, d_data.data_ptr(), d_res.data_ptr(),
                              d_index0.data_ptr(), index0_cap, d_used.data_ptr(), d_vscr.data_ptr(), sh)
         d_scr = torch.empty(max(int(self._lib.rpgpu_compress_scratch_bytes(n)), 1), dtype=torch.uint8, device=dev)
-        rc = self._lib.rpgpu_compress_plan_device(self._ctx, d_res.data_ptr(), n, codec, d_used.data_ptr(),
+        d_used.fill_(-1)  # the plan must write its total, also for an empty arena
+        rc = self._lib.rpgpu_compress_plan_device(self._ctx, d_res.data_ptr(), n,
+                                                  codec if plan_codec is None else plan_codec, d_used.data_ptr(),
                                                   d_scr.data_ptr(), sh)
         if rc != abi.RPGPU_OK:
             raise EngineError(f"rpgpu_compress_plan_device: {rc} {self.last_error()}")
         torch.cuda.synchronize(dev)
         out_bytes = int(d_used[0].item())
-        out_cap = out_bytes + abi.ARENA_TAIL_PAD
-        d_out = torch.zeros(out_cap, dtype=torch.uint8, device=dev)
+        if out_bytes < 0:
+            raise EngineError("rpgpu_compress_plan_device left *d_out_bytes unwritten")
+        if out_cap is None:
+            out_cap = out_bytes + abi.ARENA_TAIL_PAD
+            d_out = torch.zeros(out_cap, dtype=torch.uint8, device=dev)
+        else:
+            d_out = torch.full((out_bytes + 4096,), 0xA5, dtype=torch.uint8, device=dev)
+            out_cap = min(out_cap, out_bytes + 4096)
         d_cres = torch.zeros(m * 32, dtype=torch.uint8, device=dev)
         d_odescs = torch.zeros(m * 24, dtype=torch.uint8, device=dev)
         d_ores = torch.zeros(m * 64, dtype=torch.uint8, device=dev)
-        rc = self._lib.rpgpu_compress_run_device(self._ctx, d_descs.data_ptr(), n, d_data.data_ptr(), d_res.data_ptr(),
-                                                 codec, d_cres.data_ptr(), d_out.data_ptr(), out_cap,
-                                                 d_odescs.data_ptr(), d_ores.data_ptr(), d_scr.data_ptr(), sh)
-        if rc != abi.RPGPU_OK:
-            raise EngineError(f"rpgpu_compress_run_device: {rc} {self.last_error()}")
+        for _ in range(runs):  # a plan may be run any number of times
+            rc = self._lib.rpgpu_compress_run_device(self._ctx, d_descs.data_ptr(), n, d_data.data_ptr(),
+                                                     d_res.data_ptr(), codec, d_cres.data_ptr(), d_out.data_ptr(),
+                                                     out_cap, d_odescs.data_ptr(), d_ores.data_ptr(),
+                                                     d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_compress_run_device: {rc} {self.last_error()}")
         torch.cuda.synchronize(dev)
         return dict(
             results=d_res.cpu().numpy().view(abi.RESULT_DTYPE)[:n].copy(),

@@ -26,12 +26,14 @@ ROOT = Path(__file__).resolve().parents[1]
 CONDA = "/opt/conda"
 
 
-def build_fuzzer(tmp: Path, san: bool = False) -> Path:
+def build_fuzzer(tmp: Path, san: bool = False, csrc: Path | None = None) -> Path:
+    """csrc: another copy of the engine's sources to build against (tests/test_comp_bodies.py)."""
     lib = orc.build()
     exe = tmp / ("compress_fuzz_san" if san else "compress_fuzz")
     flags = ["-fsanitize=address,undefined", "-static-libstdc++", "-fno-sanitize-recover=undefined", "-g", "-O1"] \
         if san else ["-O2"]
-    r = subprocess.run(["g++", "-std=c++17", *flags, f"-I{ROOT / 'redpanda_amd' / 'csrc'}", f"-I{ROOT / 'include'}",
+    csrc = csrc or ROOT / "redpanda_amd" / "csrc"
+    r = subprocess.run(["g++", "-std=c++17", *flags, f"-I{csrc}", f"-I{ROOT / 'include'}",
                         f"-I{CONDA}/include", str(ROOT / "tests" / "native" / "compress_fuzz.cpp"), "-o", str(exe),
                         f"-L{lib.parent}", "-lrporacle", f"-Wl,-rpath,{lib.parent}", f"-Wl,-rpath,{CONDA}/lib"],
                        capture_output=True, text=True)
