@@ -1023,6 +1023,113 @@ int32_t rpgpu_batch_timequery_device(rpgpu_ctx* ctx, const rpgpu_batch_result* d
                                      const rpgpu_record_index* d_index, const rpgpu_timequery* d_queries,
                                      uint32_t nq, rpgpu_timequery_result* d_out, void* hip_stream);
 
+/* ---- REST proxy fetch rendering ---------------------------
+ * rjson_serialize_impl<kafka::fetch_response> (pandaproxy/json/requests/fetch.h:94-154)
+ * over validated and indexed batches: the body of the proxy's fetch reply,
+ * one JSON array per response.
+ *   A response (rpgpu_pp_response) is an ordered run of ranges of d_ranges and
+ *   stands for one kafka::fetch_response; a range (rpgpu_pp_range) is one
+ *   partition_response: the batches [first, first + count) of d_descs, a topic
+ *   name (topic_len bytes at topic_off of d_topics) and a partition.  Ranges
+ *   must not overlap: a batch belongs to at most one range and a range to at
+ *   most one response (the scratch holds one output offset per batch).
+ * Output per response: '[' + objects joined by ',' + ']' without whitespace,
+ * "[]" when no record is rendered (test/fetch.cc:77).  Per batch, in order
+ * (fetch.h:114-131):
+ *   - a verdict other than RPGPU_V_OK fails the response (consume_batch
+ *     throws, no body exists): RPGPU_PP_BAD_BATCH;
+ *   - a control batch (attrs & 0x20) contributes nothing, whatever its codec;
+ *   - codec != 0: RPGPU_PP_COMPRESSED.  The reference decompresses here
+ *     (maybe_decompress_batch_sync); a caller renders such batches from the
+ *     output of rpgpu_decomp_run_device (its d_out, descriptors, results and
+ *     index).  A response mixing both kinds needs two arenas: the caller
+ *     splits it;
+ *   - index_count != record_count (validated without RPGPU_OP_INDEX, or the
+ *     index was cut): RPGPU_PP_NOT_INDEXED.
+ * Per record (fetch.h:46-82, test/fetch.cc:95-96), keys in this order:
+ *   {"topic":"<name>","key":K,"value":V,"partition":<int32>,"offset":<int64>}
+ * offset is the index entry's offset (base_offset + offset_delta as the engine
+ * wrapped it) in decimal, K and V are null when the length is <= 0 (a null
+ * and an empty field are both an empty iobuf, pandaproxy/json/iobuf.h:84-86),
+ * else '"' + base64 + '"' (iobuf.h:83-89, utils/base64.cc:74-112: the
+ * standard alphabet, '=' padding, no line breaks).  Record headers are not
+ * rendered.  format: serialization_format::none (0) and binary_v2 (3) both
+ * take this path (iobuf.h:70-73); any other value returns RPGPU_EINVAL
+ * (json_v2 re-parses every value, iobuf.h:91-101: not on the device).
+ * Topic names must pass model::validate_kafka_topic_name
+ * (model/validation.cc:20-38: 1..249 bytes of [A-Za-z0-9._-], not "." or
+ * ".."), so they need no JSON escaping; anything else, or a name outside
+ * d_topics, is RPGPU_PP_BAD_TOPIC.  A range running past n, or a response
+ * running past nranges, is RPGPU_PP_BAD_RANGE.
+ * A response's status is that of its first offending item in range order,
+ * then batch order; a range's own defects (topic, then bounds) come before
+ * its batches'.  bad_batch: the offending batch's index in d_descs
+ * (BAD_BATCH, COMPRESSED, NOT_INDEXED), the offending range's index in
+ * d_ranges (BAD_TOPIC, BAD_RANGE; nranges for a response past nranges), else
+ * 0.  A failed response has out_len 0 and writes nothing.
+ * Plan, then run, on the same stream and scratch.  The plan fills every
+ * result row (status, records, the exact out_len, out_off: an exclusive scan
+ * of the lengths, every slot on a 16-byte boundary) and *d_out_bytes.  The
+ * run writes exactly out_len bytes at out_off of every OK response, nothing
+ * between the slots and nothing at or past out_cap; a response whose slot
+ * ends past out_cap becomes RPGPU_PP_NO_ROOM (out_off and out_len kept: what
+ * it needs) and writes nothing.  A plan may be run any number of times; every
+ * run rewrites all result rows.  Wire and on-disk arenas are both accepted
+ * (key / value offsets are relative to the batch start in both); d_out must
+ * not overlap d_data. */
+enum rpgpu_pp_format { RPGPU_PP_FMT_NONE = 0, RPGPU_PP_FMT_BINARY_V2 = 3 };
+enum rpgpu_pp_status {
+    RPGPU_PP_OK = 0,
+    RPGPU_PP_BAD_BATCH,
+    RPGPU_PP_COMPRESSED,
+    RPGPU_PP_NOT_INDEXED,
+    RPGPU_PP_BAD_TOPIC,
+    RPGPU_PP_BAD_RANGE,
+    RPGPU_PP_NO_ROOM,
+};
+typedef struct rpgpu_pp_range {
+    uint32_t first;      /* first batch of the partition_response in d_descs */
+    uint32_t count;
+    uint32_t topic_off;  /* the topic name in d_topics                        */
+    uint16_t topic_len;
+    uint16_t reserved0;
+    int32_t partition;
+    uint32_t reserved1;
+} rpgpu_pp_range;        /* 24 bytes */
+typedef struct rpgpu_pp_response {
+    uint32_t first_range;
+    uint32_t range_count;
+} rpgpu_pp_response;     /* 8 bytes */
+typedef struct rpgpu_pp_result {
+    uint64_t out_off;    /* the response's JSON in d_out                      */
+    uint64_t out_len;
+    uint32_t records;    /* objects in the array                              */
+    int32_t status;      /* enum rpgpu_pp_status                              */
+    uint32_t bad_batch;
+    uint32_t reserved;
+} rpgpu_pp_result;       /* 32 bytes */
+/* The longest key or value a record's own lane encodes; a longer one is
+ * encoded by a whole wavefront.  On 512 MiB arenas the lane path measured
+ * faster at 16, 64 and 128-byte values, the wave path at 256 and 1,024
+ * bytes. */
+#define RPGPU_PP_LANE_FIELD_MAX 128
+
+size_t rpgpu_pp_fetch_scratch_bytes(uint32_t n, uint32_t nranges, uint32_t nresponses);
+int32_t rpgpu_pp_fetch_plan_device(rpgpu_ctx* ctx, const rpgpu_batch_desc* d_descs,
+                                   const rpgpu_batch_result* d_results, uint32_t n,
+                                   const rpgpu_record_index* d_index, const uint8_t* d_topics, uint32_t topics_len,
+                                   const rpgpu_pp_range* d_ranges, uint32_t nranges,
+                                   const rpgpu_pp_response* d_responses, uint32_t nresponses, int32_t format,
+                                   rpgpu_pp_result* d_out_results, uint64_t* d_out_bytes, void* d_scratch,
+                                   void* hip_stream);
+int32_t rpgpu_pp_fetch_run_device(rpgpu_ctx* ctx, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                  const rpgpu_batch_result* d_results, uint32_t n,
+                                  const rpgpu_record_index* d_index, const uint8_t* d_topics,
+                                  const rpgpu_pp_range* d_ranges, uint32_t nranges,
+                                  const rpgpu_pp_response* d_responses, uint32_t nresponses, uint8_t* d_out,
+                                  uint64_t out_cap, rpgpu_pp_result* d_out_results, void* d_scratch,
+                                  void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

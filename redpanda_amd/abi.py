@@ -161,6 +161,16 @@ FETCH_SUMMARY_DTYPE = np.dtype([("base_offset", "<i8"), ("last_offset", "<i8"), 
                                 ("bytes", "<u8"), ("record_count", "<u4"), ("has_first_tx", "u1"),
                                 ("reserved0", "u1"), ("reserved1", "<u2"), ("status", "<i4"), ("reserved2", "<u4")])
 assert FETCH_SUMMARY_DTYPE.itemsize == 48  # rpgpu_compaction_keep_device keep[] values
+# REST proxy fetch rendering (rpgpu_pp_fetch_*)
+PP_FMT_NONE, PP_FMT_BINARY_V2 = 0, 3
+(PP_OK, PP_BAD_BATCH, PP_COMPRESSED, PP_NOT_INDEXED, PP_BAD_TOPIC, PP_BAD_RANGE, PP_NO_ROOM) = range(7)
+PP_LANE_FIELD_MAX = 128  # RPGPU_PP_LANE_FIELD_MAX
+PP_RANGE_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("topic_off", "<u4"), ("topic_len", "<u2"),
+                           ("reserved0", "<u2"), ("partition", "<i4"), ("reserved1", "<u4")])
+PP_RESPONSE_DTYPE = np.dtype([("first_range", "<u4"), ("range_count", "<u4")])
+PP_RESULT_DTYPE = np.dtype([("out_off", "<u8"), ("out_len", "<u8"), ("records", "<u4"), ("status", "<i4"),
+                            ("bad_batch", "<u4"), ("reserved", "<u4")])
+assert PP_RANGE_DTYPE.itemsize == 24 and PP_RESPONSE_DTYPE.itemsize == 8 and PP_RESULT_DTYPE.itemsize == 32
 INDEX_ENTRY_DTYPE = np.dtype([("relative_offset", "<u4"), ("relative_time", "<u4"), ("position", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 32 and SEGMENT_STATE_DTYPE.itemsize == 48 and INDEX_ENTRY_DTYPE.itemsize == 16
 assert INDEX_DTYPE.itemsize == 32 and RP_HEADER_DTYPE.itemsize == 61
@@ -295,6 +305,11 @@ def lib() -> C.CDLL:
         _sig(L.rpgpu_convert_message_set, _i32, _vp, _vp, C.c_size_t, C.c_int64, _vp, C.c_size_t,
              C.POINTER(C.c_size_t))
         _sig(L.rpgpu_legacy_kafka_error_code, _i32, _vp, _vp, _u32)
+        _sig(L.rpgpu_pp_fetch_scratch_bytes, C.c_size_t, _u32, _u32, _u32)
+        _sig(L.rpgpu_pp_fetch_plan_device, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _i32,
+             _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_pp_fetch_run_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u64,
+             _vp, _vp, _vp)
         _LIB = L
     return _LIB
 
@@ -332,4 +347,5 @@ EXPORTED = [
     "rpgpu_set_max_timestamp", "rpgpu_set_max_timestamp_device",
     "rpgpu_crc32_ranges_device", "rpgpu_crc32_extend", "rpgpu_legacy_scratch_bytes", "rpgpu_legacy_plan_device",
     "rpgpu_legacy_run_device", "rpgpu_convert_message_set", "rpgpu_legacy_kafka_error_code",
+    "rpgpu_pp_fetch_scratch_bytes", "rpgpu_pp_fetch_plan_device", "rpgpu_pp_fetch_run_device",
 ]

@@ -114,6 +114,18 @@ hipError_t launch_legacy_run(const rpgpu_batch_desc* d_sets, uint32_t n, const u
                              rpgpu_batch_desc* d_out_descs, rpgpu_batch_result* d_vres2, rpgpu_record_index* d_index,
                              uint64_t index_cap, uint64_t* d_index_used, void* d_scratch, const uint32_t* d_tables,
                              const uint32_t* d_tables32, int grid, uint32_t lane_max, hipStream_t s);
+size_t pp_fetch_scratch_bytes(uint32_t n, uint32_t nranges, uint32_t nresponses);
+hipError_t launch_pp_fetch_plan(const rpgpu_batch_result* d_results, uint32_t n, const rpgpu_record_index* d_index,
+                                const uint8_t* d_topics, uint32_t topics_len, const rpgpu_pp_range* d_ranges,
+                                uint32_t nranges, const rpgpu_pp_response* d_responses, uint32_t nresponses,
+                                rpgpu_pp_result* d_out_results, uint64_t* d_out_bytes, void* d_scratch,
+                                hipStream_t s);
+hipError_t launch_pp_fetch_run(const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                               const rpgpu_batch_result* d_results, uint32_t n, const rpgpu_record_index* d_index,
+                               const uint8_t* d_topics, const rpgpu_pp_range* d_ranges, uint32_t nranges,
+                               const rpgpu_pp_response* d_responses, uint32_t nresponses, uint8_t* d_out,
+                               uint64_t out_cap, rpgpu_pp_result* d_out_results, void* d_scratch, uint32_t lane_max,
+                               hipStream_t s);
 }  // namespace rpgpu
 
 namespace {
@@ -167,6 +179,9 @@ struct rpgpu_ctx {
     // each, longer ones by a wave each: on 1 GiB arenas the lane path measured faster at
     // 138 and 438-byte ranges, the wave path at 1,058 and 4,034 bytes
     uint32_t legacy_lane_max = 512;
+    // REST proxy fetch: keys and values up to this many bytes are encoded by their
+    // record's lane, longer ones by a wave each (the sweep behind the value: DESIGN.md §3)
+    uint32_t pp_lane_max = RPGPU_PP_LANE_FIELD_MAX;
     int64_t* d_sum_partial = nullptr;  // partition summaries: per-workgroup tables
     DevBuf work;     // submissions: descs | data | results | index | scratch | used
     DevBuf small;    // scalar mirrors
@@ -309,6 +324,13 @@ rpgpu_ctx* rpgpu_open(int device, const rpgpu_opts* opts) {
         char* end = nullptr;
         const unsigned long v = strtoul(lm, &end, 10);
         if (end != lm && *end == 0 && v <= 0xffffffffull) c->legacy_lane_max = (uint32_t)v;
+    }
+    // diagnostics (scripts/pp_fetch_bench.py --lane-field), not part of the ABI:
+    // the lane / wave boundary of the REST proxy rendering in bytes, read the same way
+    if (const char* lm = getenv("RPGPU_PP_LANE_FIELD")) {
+        char* end = nullptr;
+        const unsigned long v = strtoul(lm, &end, 10);
+        if (end != lm && *end == 0 && v <= 0x7fffffffull) c->pp_lane_max = (uint32_t)v;
     }
     // not fatal: without it the summaries take the global-atomic path
     if (hipMalloc(&c->d_sum_partial, rpgpu::summary_scratch_bytes(c->cu_count)) != hipSuccess)
@@ -462,6 +484,46 @@ int32_t rpgpu_kafka_serialize_device(rpgpu_ctx* c, const uint8_t* d_data, const 
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     hipError_t e = rpgpu::launch_kafka_serialize(d_data, d_descs, d_terms, n, d_out, d_ranges, nranges, d_summaries, s);
     if (e != hipSuccess) return fail(c, e, "serialize launch");
+    return RPGPU_OK;
+}
+
+size_t rpgpu_pp_fetch_scratch_bytes(uint32_t n, uint32_t nranges, uint32_t nresponses) {
+    return rpgpu::pp_fetch_scratch_bytes(n, nranges, nresponses);
+}
+
+int32_t rpgpu_pp_fetch_plan_device(rpgpu_ctx* c, const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_results,
+                                   uint32_t n, const rpgpu_record_index* d_index, const uint8_t* d_topics,
+                                   uint32_t topics_len, const rpgpu_pp_range* d_ranges, uint32_t nranges,
+                                   const rpgpu_pp_response* d_responses, uint32_t nresponses, int32_t format,
+                                   rpgpu_pp_result* d_out_results, uint64_t* d_out_bytes, void* d_scratch,
+                                   void* hip_stream) {
+    // serialization_format::none and binary_v2 share the base64 path (pandaproxy/json/iobuf.h:70-73)
+    if (!c || (format != RPGPU_PP_FMT_NONE && format != RPGPU_PP_FMT_BINARY_V2) ||
+        (n && (!d_descs || !d_results)) || (nranges && !d_ranges) || (topics_len && !d_topics) ||
+        (nresponses && (!d_responses || !d_out_results || !d_scratch)))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_pp_fetch_plan(d_results, n, d_index, d_topics, topics_len, d_ranges, nranges,
+                                               d_responses, nresponses, d_out_results, d_out_bytes, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "pandaproxy fetch plan launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_pp_fetch_run_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                  const rpgpu_batch_result* d_results, uint32_t n, const rpgpu_record_index* d_index,
+                                  const uint8_t* d_topics, const rpgpu_pp_range* d_ranges, uint32_t nranges,
+                                  const rpgpu_pp_response* d_responses, uint32_t nresponses, uint8_t* d_out,
+                                  uint64_t out_cap, rpgpu_pp_result* d_out_results, void* d_scratch,
+                                  void* hip_stream) {
+    if (!c || (n && (!d_data || !d_descs || !d_results)) || (nranges && !d_ranges) ||
+        (nresponses && (!d_responses || !d_out_results || !d_scratch)) || (out_cap && !d_out) ||
+        (n && d_data == d_out))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_pp_fetch_run(d_data, d_descs, d_results, n, d_index, d_topics, d_ranges, nranges,
+                                              d_responses, nresponses, d_out, out_cap, d_out_results, d_scratch,
+                                              c->pp_lane_max, s);
+    if (e != hipSuccess) return fail(c, e, "pandaproxy fetch run launch");
     return RPGPU_OK;
 }
 

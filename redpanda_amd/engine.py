@@ -586,6 +586,62 @@ class Engine:
         return (d_out.cpu().numpy()[: data.size].copy(),
                 d_sums.cpu().numpy().view(abi.FETCH_SUMMARY_DTYPE)[:nr].copy())
 
+    def pp_fetch_json(self, data: np.ndarray, descs: np.ndarray, results: np.ndarray, index: np.ndarray,
+                      topics: bytes | np.ndarray, ranges: np.ndarray, responses: np.ndarray, fmt: int = 3,
+                      out_cap: int | None = None, plans: int = 1, runs: int = 1, fill: int = 0, guard: int = 0):
+        """rpgpu_pp_fetch_plan_device / rpgpu_pp_fetch_run_device: the REST proxy's
+        fetch reply (rjson_serialize_impl<kafka::fetch_response>) for every
+        response, from a validated and indexed arena.  Returns (out, results):
+        the output buffer (out_cap bytes, the plan's size by default, then
+        `guard` more; all pre-filled with `fill`) and the rpgpu_pp_result rows;
+        response i is out[out_off:out_off + out_len].  plans / runs: how often
+        each stage is enqueued (a plan may be run any number of times)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        descs = np.ascontiguousarray(descs, dtype=abi.DESC_DTYPE)
+        results = np.ascontiguousarray(results, dtype=abi.RESULT_DTYPE)
+        index = np.ascontiguousarray(index, dtype=abi.INDEX_DTYPE)
+        topics = np.frombuffer(bytes(topics), dtype=np.uint8) if not isinstance(topics, np.ndarray) else topics
+        ranges = np.ascontiguousarray(ranges, dtype=abi.PP_RANGE_DTYPE)
+        responses = np.ascontiguousarray(responses, dtype=abi.PP_RESPONSE_DTYPE)
+        n, nr, nq = len(descs), len(ranges), len(responses)
+        if len(results) != n:
+            raise ValueError("one result row per descriptor")
+
+        def up(a):
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(64, np.uint8)).to(dev)
+
+        d_data = up(np.concatenate([data, np.zeros(abi.ARENA_TAIL_PAD, np.uint8)]))
+        d_descs, d_res, d_idx, d_top, d_rg, d_rs = (up(a) for a in (descs, results, index, topics, ranges, responses))
+        d_pres = torch.zeros(max(nq, 1) * abi.PP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_bytes = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_scr = torch.zeros(max(int(self._lib.rpgpu_pp_fetch_scratch_bytes(n, nr, nq)), 1), dtype=torch.uint8,
+                            device=dev)
+        for _ in range(plans):
+            rc = self._lib.rpgpu_pp_fetch_plan_device(self._ctx, d_descs.data_ptr(), d_res.data_ptr(), n,
+                                                      d_idx.data_ptr(), d_top.data_ptr(), len(topics),
+                                                      d_rg.data_ptr(), nr, d_rs.data_ptr(), nq, fmt,
+                                                      d_pres.data_ptr(), d_bytes.data_ptr(), d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_pp_fetch_plan_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        if out_cap is None:
+            out_cap = int(d_bytes.item())
+        d_out = torch.full((max(out_cap + guard, 1),), fill, dtype=torch.uint8, device=dev)
+        for _ in range(runs):
+            rc = self._lib.rpgpu_pp_fetch_run_device(self._ctx, d_data.data_ptr(), d_descs.data_ptr(),
+                                                     d_res.data_ptr(), n, d_idx.data_ptr(), d_top.data_ptr(),
+                                                     d_rg.data_ptr(), nr, d_rs.data_ptr(), nq, d_out.data_ptr(),
+                                                     out_cap, d_pres.data_ptr(), d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_pp_fetch_run_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return (d_out.cpu().numpy()[: out_cap + guard].copy(),
+                d_pres.cpu().numpy().view(abi.PP_RESULT_DTYPE)[:nq].copy())
+
     def batch_timequery(self, results: np.ndarray, index: np.ndarray, queries: np.ndarray) -> np.ndarray:
         """rpgpu_batch_timequery_device (storage::batch_timequery) per query."""
         import torch
