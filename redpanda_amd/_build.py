@@ -40,6 +40,12 @@ def _run(cmd: list[str]) -> None:
         raise RuntimeError(f"build failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
 
 
+def rpgpu_flags() -> list[str]:
+    """hipcc flags of every librpgpu.so translation unit (tests/test_kernel_resources.py
+    compiles with the same ones)."""
+    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
+
+
 def build_rpgpu(force: bool = False) -> Path:
     srcs = [CSRC / s for s in RPGPU_SRCS + RPGPU_HDRS] + [INCLUDE / "rpgpu.h"]
     if force or _stale(LIBRPGPU, srcs):
@@ -48,7 +54,7 @@ def build_rpgpu(force: bool = False) -> Path:
 
         obj = ROOT / "build" / "obj"
         obj.mkdir(parents=True, exist_ok=True)
-        flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}"]
+        flags = rpgpu_flags()
         objs = [obj / (s + ".o") for s in RPGPU_SRCS]
         jobs = max(1, min(len(objs), os.cpu_count() or 1, 8))
         with ThreadPoolExecutor(jobs) as ex:

@@ -1,7 +1,13 @@
 // rpgpu_kernels.hip — CDNA4 (gfx950) kernels of the record-batch engine.
 //
 // validate_kernel: one wavefront owns one batch at a time (grid-stride over
-// the arena, 16 waves per CU).  Two phases per group of 64 batches:
+// the arena; 8 workgroups of 4 waves per CU, i.e. 8 waves per SIMD, which the
+// kernel fits only within 64 VGPRs and without scratch memory:
+// tests/test_kernel_resources.py).  32 of those registers are the rows in
+// flight, so the per-batch section keeps nothing wide: the parsed header
+// lives as one little-endian image from which the result fields, the header
+// CRC window and the body-CRC image are read, and the batch's result is
+// assembled one dword per lane and stored once.  Two passes over the arena:
 //
 // (1) CRC32C, all 64 lanes on one batch ("strided rows").  The Kafka CRC
 // covers batch bytes [21, n) (kafka_batch_adapter.cc:99-134).  The region is
@@ -59,47 +65,37 @@ struct Stamps {
     } while (0)
 #endif
 
-// Parsed record_batch_header (model/record.h:356-440), wave-uniform.
-struct Header {
-    int32_t size_bytes;
-    int64_t base_offset;
-    int32_t type;  // int8 in the reference; kept 32-bit so the struct has no padding
-    int32_t crc;
-    int16_t attrs;
-    int32_t last_offset_delta;
-    int64_t first_ts, max_ts, producer_id;
-    int16_t producer_epoch;
-    int32_t base_sequence, record_count;
-};
+// v with lane i < 16 holding dword i of the wave-uniform image
+__device__ __forceinline__ uint32_t lanes16(const Img64& I) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) v = writelane(v, I.w[i], i);
+    return v;
+}
 
-struct Result {
-    int32_t verdict;
-    uint32_t crc, crc_expected, header_crc;
-    Header h;
-    uint32_t index_first, index_count;
+// A batch's rpgpu_batch_result is assembled one dword per lane (lanes 0..15
+// of one VGPR) and leaves as a single 64-byte store: sixteen wave-uniform
+// values held until the end of the batch would cost the row loop sixteen
+// registers.
+enum : int {
+    kResVerdict = 0,
+    kResCrc = 1,
+    kResCrcExpected = 2,
+    kResHeaderCrc = 3,
+    kResSizeBytes = 4,
+    kResRecordCount = 5,
+    kResBaseOffset = 6,  // and 7
+    kResLastOffsetDelta = 8,
+    kResAttrsCodecType = 9,
+    kResFirstTs = 10,  // and 11
+    kResMaxTs = 12,    // and 13
+    kResIndexFirst = 14,
+    kResIndexCount = 15,
 };
-
-// Every dword goes through readfirstlane (the values are wave-uniform): this
-// keeps the SLP vectorizer from turning the field reads into vector loads of
-// the struct, which would force the struct into scratch memory.
-__device__ __forceinline__ uint32_t u32s(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ void write_result(rpgpu_batch_result* out, const Result& r) {
-    if (lane_id() == 0) {
-        const uint64_t bo = (uint64_t)r.h.base_offset, ft = (uint64_t)r.h.first_ts, mt = (uint64_t)r.h.max_ts;
-        u32x4 a = {u32s((uint32_t)r.verdict), u32s(r.crc), u32s(r.crc_expected), u32s(r.header_crc)};
-        u32x4 b = {u32s((uint32_t)r.h.size_bytes), u32s((uint32_t)r.h.record_count), u32s((uint32_t)bo),
-                   u32s((uint32_t)(bo >> 32))};
-        u32x4 c = {u32s((uint32_t)r.h.last_offset_delta),
-                   u32s((uint32_t)(uint16_t)r.h.attrs | ((uint32_t)(r.h.attrs & 7) << 16) |
-                        ((uint32_t)(uint8_t)r.h.type << 24)),
-                   u32s((uint32_t)ft), u32s((uint32_t)(ft >> 32))};
-        u32x4 d = {u32s((uint32_t)mt), u32s((uint32_t)(mt >> 32)), u32s(r.index_first), u32s(r.index_count)};
-        u32x4* o = reinterpret_cast<u32x4*>(out);
-        o[0] = a;
-        o[1] = b;
-        o[2] = c;
-        o[3] = d;
-    }
+__device__ __forceinline__ void store_result(rpgpu_batch_result* out, uint32_t rv) {
+    static_assert(sizeof(rpgpu_batch_result) == 64, "result layout");
+    const uint32_t l = lane_id();
+    if (l < 16) reinterpret_cast<uint32_t*>(out)[l] = rv;
 }
 
 __device__ __forceinline__ void load_tables(uint32_t* s, const uint32_t* __restrict__ g) {
@@ -109,26 +105,17 @@ __device__ __forceinline__ void load_tables(uint32_t* s, const uint32_t* __restr
 }
 
 // header CRC over image D[4..61) (internal_header_only_crc,
-// record_utils.cc:34-55): the 64-byte right-aligned window
-// [7 zero bytes | D[4..61)], init folded into D[4..8), one byte per lane
-// through the lane-minor tables HB (2 conflict-free lookups), then an XOR
-// reduction over the wave.
-__device__ __forceinline__ uint32_t header_crc_vec(const uint32_t* sT, const Img64& D) {
-    uint32_t win[16];
-    win[0] = 0;
-    win[1] = (D.w[1] << 24) ^ 0xff000000u;
-    win[2] = ((D.w[1] >> 8) | (D.w[2] << 24)) ^ 0x00ffffffu;
-#pragma unroll
-    for (int m = 3; m < 16; m++) win[m] = (D.w[m - 1] >> 8) | (D.w[m] << 24);
+// record_utils.cc:34-55), D given one dword per lane (lanes 0..15 of dv):
+// the 64-byte right-aligned window [7 zero bytes | D[4..61)], init folded
+// into D[4..8), one byte per lane through the lane-minor tables HB (2
+// conflict-free lookups), then an XOR reduction over the wave.
+__device__ __forceinline__ uint32_t header_crc_lanes(const uint32_t* sT, uint32_t dv) {
     const uint32_t l = lane_id();
-    // lane i < 16 holds window dword i (writelane, not a select over an
-    // array: that would be lowered to scratch memory), then every lane
-    // fetches the dword of its byte
-    uint32_t vwin = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) vwin = writelane(vwin, win[i], i);
-    const uint32_t w = __builtin_amdgcn_ds_bpermute((int)((l >> 2) << 2), vwin);
-    const uint32_t byte = (w >> (8 * (l & 3))) & 255u;
+    // lane l hashes window byte l = D byte l - 3 (lanes 0..6: the zero bytes)
+    const int32_t k = (int32_t)l - 3;
+    const uint32_t w = __builtin_amdgcn_ds_bpermute((k >> 2) << 2, dv);
+    uint32_t byte = (w >> (8 * (k & 3))) & 255u;
+    byte = l < 7 ? 0u : (l < 11 ? byte ^ 255u : byte);
     const uint32_t* hb = sT + kOffHB + l;
     uint32_t c = hb[(byte & 15u) * 64] ^ hb[(16u + (byte >> 4)) * 64];
     c ^= row_shl<1>(c);
@@ -136,6 +123,9 @@ __device__ __forceinline__ uint32_t header_crc_vec(const uint32_t* sT, const Img
     c ^= row_shl<4>(c);
     c ^= row_shl<8>(c);
     return ~(rdl(c, 0) ^ rdl(c, 16) ^ rdl(c, 32) ^ rdl(c, 48));
+}
+__device__ __forceinline__ uint32_t header_crc_vec(const uint32_t* sT, const Img64& D) {
+    return header_crc_lanes(sT, lanes16(D));
 }
 
 // Row geometry of the CRC region [21, n) of a batch: 1 KiB rows aligned to
@@ -230,21 +220,12 @@ __device__ __forceinline__ u32x4 merge_header(u32x4 y, int32_t ro0, uint32_t v_i
 // for walk_kernel.
 __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, const rpgpu_batch_desc& d,
                                               uint32_t b, const uint8_t* __restrict__ data,
-                                              rpgpu_batch_result* __restrict__ res, uint32_t index_first,
-                                              Prefetch& pf, const rpgpu_batch_desc& nd,
-                                              bool has_next DIAG_PARAM) {
+                                              rpgpu_batch_result* __restrict__ res, Prefetch& pf,
+                                              const rpgpu_batch_desc& nd, bool has_next DIAG_PARAM) {
     const uint32_t l = lane_id();
     const uint8_t* p = data + d.offset;
     const uint32_t len = d.length;
-    Result r;
-    r.verdict = RPGPU_V_OK;
-    r.crc = r.crc_expected = r.header_crc = 0;
-    r.h.size_bytes = r.h.type = r.h.crc = r.h.last_offset_delta = 0;
-    r.h.base_sequence = r.h.record_count = 0;
-    r.h.attrs = r.h.producer_epoch = 0;
-    r.h.base_offset = r.h.first_ts = r.h.max_ts = r.h.producer_id = 0;
-    r.index_first = index_first;
-    r.index_count = 0;
+    int32_t verdict = RPGPU_V_OK;
 
     // ---- 64-byte header window; the next batch's goes in flight at once
     const uint32_t hv = pf.hv;
@@ -258,7 +239,11 @@ __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, c
     pf.hv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(nrs, (int32_t)(4 * (l & 15)), 0, 0);
     if (has_next) ngm = desc_geometry(nd);
 
-    Img64 D;  // little-endian disk header image (CRC'd bytes [4, 61))
+    // The parse leaves one thing behind, the little-endian disk header image
+    // D (storage's layout, model/record.h:356-440; all zero unless the header
+    // is accepted): the result's fields, the header CRC and the body-CRC
+    // image are all read out of it, so no parsed field outlives this section.
+    Img64 D;
     D.clear();
     int64_t n;  // end of the Kafka-CRC region (trimmed batch length)
     bool body_trunc = false;
@@ -266,7 +251,7 @@ __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, c
     if (d.flags & RPGPU_DESC_NULL_RECORDS) {
         // produce.cc:440-449: the records field was null; nothing to read
         n = 0;
-        r.verdict = RPGPU_V_NULL_RECORDS;
+        verdict = RPGPU_V_NULL_RECORDS;
         fail = true;
     } else if (d.format == RPGPU_FMT_KAFKA_WIRE) {
         // kafka_batch_adapter::adapt / read_header (kafka_batch_adapter.cc:32-198)
@@ -279,48 +264,40 @@ __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, c
             body_trunc = true;
         }
         if (len < 12) {
-            r.verdict = RPGPU_V_TOO_SMALL;
+            verdict = RPGPU_V_TOO_SMALL;
             fail = true;
         } else if (n < 17) {
-            r.verdict = RPGPU_V_HDR_TRUNC_THROW;
+            verdict = RPGPU_V_HDR_TRUNC_THROW;
             fail = true;
         } else if ((int8_t)H.byte(16) != 2) {
-            r.verdict = RPGPU_V_BAD_MAGIC;
+            verdict = RPGPU_V_BAD_MAGIC;
             fail = true;
         } else if (n < kHeaderSize) {
-            r.verdict = RPGPU_V_HDR_TRUNC_THROW;
+            verdict = RPGPU_V_HDR_TRUNC_THROW;
             fail = true;
         } else {
-            r.h.size_bytes = (int32_t)((uint32_t)bl + 12u);
-            r.h.base_offset = (int64_t)H.get_be(0, 8);
-            r.h.type = 1;  // record_batch_type::raft_data
-            r.h.crc = (int32_t)H.get_be(17, 4);
-            r.h.attrs = (int16_t)H.get_be(21, 2);
-            r.h.last_offset_delta = (int32_t)H.get_be(23, 4);
-            r.h.first_ts = (int64_t)H.get_be(27, 8);
-            r.h.max_ts = (int64_t)H.get_be(35, 8);
-            r.h.producer_id = (int64_t)H.get_be(43, 8);
-            r.h.producer_epoch = (int16_t)H.get_be(51, 2);
-            r.h.base_sequence = (int32_t)H.get_be(53, 4);
-            r.h.record_count = (int32_t)H.get_be(57, 4);
-            D.put_le(4, (uint32_t)r.h.size_bytes, 4);
-            D.put_le(8, (uint64_t)r.h.base_offset, 8);
-            D.put_le(16, 1, 1);
-            D.put_le(17, (uint32_t)r.h.crc, 4);
-            D.put_le(21, (uint16_t)r.h.attrs, 2);
-            D.put_le(23, (uint32_t)r.h.last_offset_delta, 4);
-            D.put_le(27, (uint64_t)r.h.first_ts, 8);
-            D.put_le(35, (uint64_t)r.h.max_ts, 8);
-            D.put_le(43, (uint64_t)r.h.producer_id, 8);
-            D.put_le(51, (uint16_t)r.h.producer_epoch, 2);
-            D.put_le(53, (uint32_t)r.h.base_sequence, 4);
-            D.put_le(57, (uint32_t)r.h.record_count, 4);
+            D.put_le(4, (uint32_t)bl + 12u, 4);                // size_bytes
+            D.put_le(8, (uint32_t)H.get_be(4, 4), 4);          // base_offset
+            D.put_le(12, (uint32_t)H.get_be(0, 4), 4);
+            D.put_le(16, 1, 1);                                // record_batch_type::raft_data
+            D.put_le(17, (uint32_t)H.get_be(17, 4), 4);        // crc
+            D.put_le(21, (uint32_t)H.get_be(21, 2), 2);        // attrs
+            D.put_le(23, (uint32_t)H.get_be(23, 4), 4);        // last_offset_delta
+            D.put_le(27, (uint32_t)H.get_be(31, 4), 4);        // first_timestamp
+            D.put_le(31, (uint32_t)H.get_be(27, 4), 4);
+            D.put_le(35, (uint32_t)H.get_be(39, 4), 4);        // max_timestamp
+            D.put_le(39, (uint32_t)H.get_be(35, 4), 4);
+            D.put_le(43, (uint32_t)H.get_be(47, 4), 4);        // producer_id
+            D.put_le(47, (uint32_t)H.get_be(43, 4), 4);
+            D.put_le(51, (uint32_t)H.get_be(51, 2), 2);        // producer_epoch
+            D.put_le(53, (uint32_t)H.get_be(53, 4), 4);        // base_sequence
+            D.put_le(57, (uint32_t)H.get_be(57, 4), 4);        // record_count
         }
     } else {
         // storage::continuous_batch_parser read_header_impl (parser.cc:155-216)
         n = 0;
         if (len < kHeaderSize) {
-            r.verdict = RPGPU_V_STREAM_SHORT;
+            verdict = RPGPU_V_STREAM_SHORT;
             fail = true;
         } else {
             uint32_t any = 0;
@@ -328,39 +305,45 @@ __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, c
             for (int i = 0; i < 15; i++) any |= H.w[i];
             any |= H.w[15] & 0xffu;  // byte 60 only (61..63 are past the header)
             if (any == 0) {
-                r.verdict = RPGPU_V_FALLOCATED_ZERO;
+                verdict = RPGPU_V_FALLOCATED_ZERO;
                 fail = true;
             } else {
 #pragma unroll
                 for (int i = 0; i < 16; i++) D.w[i] = H.w[i];
                 D.w[15] &= 0xffu;
-                r.h.size_bytes = (int32_t)H.get_le(4, 4);
-                r.h.base_offset = (int64_t)H.get_le(8, 8);
-                r.h.type = (int8_t)H.byte(16);
-                r.h.crc = (int32_t)H.get_le(17, 4);
-                r.h.attrs = (int16_t)H.get_le(21, 2);
-                r.h.last_offset_delta = (int32_t)H.get_le(23, 4);
-                r.h.first_ts = (int64_t)H.get_le(27, 8);
-                r.h.max_ts = (int64_t)H.get_le(35, 8);
-                r.h.producer_id = (int64_t)H.get_le(43, 8);
-                r.h.producer_epoch = (int16_t)H.get_le(51, 2);
-                r.h.base_sequence = (int32_t)H.get_le(53, 4);
-                r.h.record_count = (int32_t)H.get_le(57, 4);
-                n = (int64_t)r.h.size_bytes;
+                n = (int64_t)(int32_t)D.w[1];  // size_bytes
             }
         }
     }
     const bool is_disk = d.format != RPGPU_FMT_KAFKA_WIRE;
     const bool recrc = is_disk && (d.ops & RPGPU_OP_RECRC);
+    const int32_t size_bytes = (int32_t)D.w[1];
+    const uint32_t attrs = (uint32_t)D.get_le(21, 2);
+    uint32_t crc_expected = (uint32_t)D.get_le(17, 4);
+    uint32_t rv = 0;  // the result, dword i in lane i (index_first / index_count: 0, the walk's)
+    rv = writelane(rv, (uint32_t)size_bytes, kResSizeBytes);
+    rv = writelane(rv, (uint32_t)D.get_le(57, 4), kResRecordCount);
+    rv = writelane(rv, D.w[2], kResBaseOffset);
+    rv = writelane(rv, D.w[3], kResBaseOffset + 1);
+    rv = writelane(rv, (uint32_t)D.get_le(23, 4), kResLastOffsetDelta);
+    rv = writelane(rv, attrs | ((attrs & 7u) << 16) | (D.byte(16) << 24), kResAttrsCodecType);
+    rv = writelane(rv, (uint32_t)D.get_le(27, 4), kResFirstTs);
+    rv = writelane(rv, (uint32_t)D.get_le(31, 4), kResFirstTs + 1);
+    rv = writelane(rv, (uint32_t)D.get_le(35, 4), kResMaxTs);
+    rv = writelane(rv, (uint32_t)D.get_le(39, 4), kResMaxTs + 1);
+    rv = writelane(rv, crc_expected, kResCrcExpected);
+    uint32_t dv = 0;  // D, dword i in lane i (kept for the re-checksummed header)
     if (!fail) {
-        r.crc_expected = (uint32_t)r.h.crc;
-        if (!recrc && ((d.ops & RPGPU_OP_HDRCRC) || is_disk)) r.header_crc = header_crc_vec(sT, D);
+        dv = lanes16(D);
+        uint32_t header_crc = 0;
+        if (!recrc && ((d.ops & RPGPU_OP_HDRCRC) || is_disk)) header_crc = header_crc_lanes(sT, dv);
+        rv = writelane(rv, header_crc, kResHeaderCrc);
         if (is_disk) {
-            if (!recrc && r.header_crc != H.w[0]) {
-                r.verdict = RPGPU_V_HDR_CRC_MISMATCH;
+            if (!recrc && header_crc != H.w[0]) {
+                verdict = RPGPU_V_HDR_CRC_MISMATCH;
                 fail = true;
-            } else if (r.h.size_bytes < kHeaderSize || (int64_t)r.h.size_bytes > (int64_t)len) {
-                r.verdict = RPGPU_V_STREAM_SHORT;
+            } else if (size_bytes < kHeaderSize || (int64_t)size_bytes > (int64_t)len) {
+                verdict = RPGPU_V_STREAM_SHORT;
                 fail = true;
             }
         }
@@ -369,27 +352,33 @@ __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, c
         // nothing of this batch is checksummed: just move the next one's rows
         load_rows(pf.x, nrs, ngm, 0, l);
         pf.gm = ngm;
-        write_result(res + b, r);
+        rv = writelane(rv, (uint32_t)verdict, kResVerdict);
+        store_result(res + b, rv);
         return;
     }
 
     // ---- body-CRC image: bytes [21, 61) big-endian (record_utils.cc:68-80),
-    //      bytes < 21 zero, init 0xFFFFFFFF folded into [21, 25)
-    Img64 B;
-    B.clear();
-    B.put_be(21, (uint16_t)r.h.attrs, 2);
-    B.put_be(23, (uint32_t)r.h.last_offset_delta, 4);
-    B.put_be(27, (uint64_t)r.h.first_ts, 8);
-    B.put_be(35, (uint64_t)r.h.max_ts, 8);
-    B.put_be(43, (uint64_t)r.h.producer_id, 8);
-    B.put_be(51, (uint16_t)r.h.producer_epoch, 2);
-    B.put_be(53, (uint32_t)r.h.base_sequence, 4);
-    B.put_be(57, (uint32_t)r.h.record_count, 4);
-    B.w[5] ^= 0xffffff00u;  // bytes 21..23
-    B.w[6] ^= 0x000000ffu;  // byte 24
-    uint32_t v_img = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) v_img = (l == (uint32_t)i) ? B.w[i] : v_img;
+    //      bytes < 21 zero, init 0xFFFFFFFF folded into [21, 25); dword i in
+    //      lane i of v_img
+    uint32_t v_img;
+    {
+        Img64 B;
+        B.clear();
+        B.put_be(21, attrs, 2);
+        B.put_be(23, (uint32_t)D.get_le(23, 4), 4);  // last_offset_delta
+        B.put_be(27, (uint32_t)D.get_le(31, 4), 4);  // first_timestamp
+        B.put_be(31, (uint32_t)D.get_le(27, 4), 4);
+        B.put_be(35, (uint32_t)D.get_le(39, 4), 4);  // max_timestamp
+        B.put_be(39, (uint32_t)D.get_le(35, 4), 4);
+        B.put_be(43, (uint32_t)D.get_le(47, 4), 4);  // producer_id
+        B.put_be(47, (uint32_t)D.get_le(43, 4), 4);
+        B.put_be(51, (uint32_t)D.get_le(51, 2), 2);  // producer_epoch
+        B.put_be(53, (uint32_t)D.get_le(53, 4), 4);  // base_sequence
+        B.put_be(57, (uint32_t)D.get_le(57, 4), 4);  // record_count
+        B.w[5] ^= 0xffffff00u;  // bytes 21..23
+        B.w[6] ^= 0x000000ffu;  // byte 24
+        v_img = lanes16(B);
+    }
 
     // ---- rows over the CRC region [21, n)
     const Geom gm = geometry((int32_t)n);
@@ -427,38 +416,40 @@ __device__ __forceinline__ void process_batch(const uint32_t* __restrict__ sT, c
     c = combine64(sT + kOffW, c);
     if (nrows != gm.niter) c = apply8(sT + kOffU + (nrows - gm.niter) * 128, c);
 #endif
-    r.crc = ~rdl(c, 0);
+    uint32_t crc = ~rdl(c, 0);
 #if defined(RPGPU_DIAG_NO_COMBINE) || defined(RPGPU_DIAG_NO_LOOKUP)  // keep verdicts OK
     asm volatile("" ::"v"(c));  // keep the row loads (the CRC is discarded)
-    r.crc = r.crc_expected;
+    crc = crc_expected;
 #endif
+    rv = writelane(rv, crc, kResCrc);
     if (recrc) {
         // reset_size_checksum_metadata: crc first, then the header CRC over a
-        // header that carries it
-        r.crc_expected = r.crc;
-        r.h.crc = (int32_t)r.crc;
-        D.put_le(17, r.crc, 4);
-        r.header_crc = header_crc_vec(sT, D);
+        // header that carries it (D bytes [17, 21))
+        crc_expected = crc;
+        dv = writelane(dv, (rdl(dv, 4) & 0x000000ffu) | (crc << 8), 4);
+        dv = writelane(dv, (rdl(dv, 5) & 0xffffff00u) | (crc >> 24), 5);
+        rv = writelane(rv, crc_expected, kResCrcExpected);
+        rv = writelane(rv, header_crc_lanes(sT, dv), kResHeaderCrc);
     }
     STAMP(2);
 
     // ---- verdict precedence (kafka_batch_adapter.cc:169-193)
-    const uint8_t codec = (uint8_t)(r.h.attrs & 7);
-    if (r.crc != r.crc_expected) {
-        r.verdict = RPGPU_V_CRC_MISMATCH;
+    if (crc != crc_expected) {
+        verdict = RPGPU_V_CRC_MISMATCH;
     } else if (body_trunc) {
-        r.verdict = RPGPU_V_BODY_TRUNC_THROW;
-    } else if (codec > 4) {
-        r.verdict = RPGPU_V_BAD_CODEC_THROW;
+        verdict = RPGPU_V_BODY_TRUNC_THROW;
+    } else if ((attrs & 7u) > 4) {
+        verdict = RPGPU_V_BAD_CODEC_THROW;
     }
-    write_result(res + b, r);
+    rv = writelane(rv, (uint32_t)verdict, kResVerdict);
+    store_result(res + b, rv);
     STAMP(3);
 }
 
 // One wave per batch, grid-stride: header, both CRCs and the verdict.  The
 // record walk and each batch's index_first are walk_kernel's /
 // walk_wave_kernel's (the plan's local_first / block_base are theirs too).
-__global__ __launch_bounds__(kValidateThreads) void validate_kernel(
+__global__ __launch_bounds__(kValidateThreads, 8) void validate_kernel(
     const rpgpu_batch_desc* __restrict__ descs, uint32_t b0, uint32_t n, const uint8_t* __restrict__ data,
     rpgpu_batch_result* __restrict__ res, rpgpu_record_index* __restrict__ index,
     const uint32_t* __restrict__ local_first, const uint32_t* __restrict__ caps,
@@ -491,7 +482,7 @@ __global__ __launch_bounds__(kValidateThreads) void validate_kernel(
         const rpgpu_batch_desc nd = sload_desc(descs + (has_next ? b + nw : b));
         // index_first is the walk's to write (walk_kernel): the checksums do not
         // wait for the plan
-        process_batch(sT, d, b, data, res, 0u, pf, nd, has_next DIAG_PASS);
+        process_batch(sT, d, b, data, res, pf, nd, has_next DIAG_PASS);
         STAMP(5);
     }
 #ifdef RPGPU_DIAG_STAMPS
