@@ -1130,6 +1130,171 @@ int32_t rpgpu_pp_fetch_run_device(rpgpu_ctx* ctx, const uint8_t* d_data, const r
                                   uint64_t out_cap, rpgpu_pp_result* d_out_results, void* d_scratch,
                                   void* hip_stream);
 
+/* ---- log append (the end of the produce call stack) -----------
+ * disk_log_appender::operator() (storage/disk_log_appender.cc:71-135) and
+ * storage::write -> disk_header_to_iobuf (storage/segment_appender_utils.cc:
+ * 28-61) over a validated arena: the batches the produce handler accepted
+ * leave the device as the bytes each partition's segment files receive.
+ * Call order on the produce path: validate -> rpgpu_set_max_timestamp_device
+ * -> rpgpu_kafka_error_codes_device -> append.
+ *
+ * The caller supplies a dense range of logs (rpgpu_append_log, nlogs rows):
+ * the batch of descriptor i belongs to log desc.partition - part_lo, the
+ * sharding convention of rpgpu_partition_summaries_device.  A batch is
+ * eligible when its verdict is RPGPU_V_OK, its partition lies in [part_lo,
+ * part_lo + nlogs) and d_codes is NULL or d_codes[i] == 0 (d_codes: the
+ * output of rpgpu_kafka_error_codes_device, so a batch over batch_max_bytes
+ * is not appended, produce.cc:317-324).  Every other batch is skipped: the
+ * handler answers it with an error and never appends it.  (RPGPU_V_OK implies
+ * 61 <= size_bytes <= desc.length; a result row that breaks this is skipped.)
+ *
+ * Per log, the eligible batches in descriptor order go through the appender:
+ *   idx = log.next_offset; last = INT64_MIN (model::offset{}); byte_size = 0
+ *   left = ROLL_FIRST ? 0 : (max_segment_size > file_offset
+ *                            ? max_segment_size - file_offset : 0)
+ *   pos  = file_offset
+ *   for each eligible batch b:
+ *       base = idx                                  (disk_log_appender.cc:73)
+ *       if left == 0:                 (needs_to_roll_log, :61 and :80-97)
+ *           new segment {base_offset = idx, file position 0, ROLLED}; pos = 0
+ *           left = max_segment_size   (initialize() -> bytes_left_before_roll())
+ *       if b.type == ghost_batch (7):               (:111-117, on-disk input)
+ *           last = base + lod; idx = last + 1; continue   (GHOST, no bytes)
+ *       write the 61-byte header + body at pos      (segment.cc:507-531)
+ *       pos += size_bytes; byte_size += size_bytes
+ *       left -= min(left, size_bytes)               (:119-132)
+ *       last = base + lod; idx = last + 1
+ * RPGPU_APPEND_ROLL_FIRST is the caller's statement that the log has no
+ * segment or appender, or that the batches' term differs from the log's
+ * (needs_to_roll_log); the term is neither serialized nor part of the header
+ * CRC, so nothing else of it is needed.  max_segment_size == 0 makes the
+ * reference's do_until spin forever: such a log gets RPGPU_APPEND_BAD_CONFIG
+ * and appends nothing (its batches are RPGPU_APPEND_SKIPPED).  Offsets wrap in
+ * 64-bit arithmetic as in rpgpu_segment_index_device; the precondition is
+ * next_offset + sum(lod + 1) <= INT64_MAX (signed overflow of model::offset
+ * is undefined in the reference).
+ *
+ * The written header (disk_header_to_iobuf, little-endian): size_bytes is
+ * batch_length + 12 for wire input and the stored value for on-disk input;
+ * base_offset is `base`; type is 1 (raft_data, as read_header sets it) for
+ * wire input and the stored type for on-disk input; crc, attrs,
+ * last_offset_delta, both timestamps, producer id and epoch, base sequence
+ * and record count are taken from the batch bytes, so a batch re-stamped by
+ * rpgpu_set_max_timestamp_device is appended as stamped; header_crc is
+ * internal_header_only_crc of the above (CRC32C of bytes [4, 61)).  The body
+ * is the size_bytes - 61 bytes after the input header: trailing bytes of a
+ * wire descriptor past batch_length + 12 are not copied, compressed batches
+ * are appended as they are.
+ *
+ * Output.  Log l's bytes form one region at out_offset (an exclusive scan of
+ * the logs' byte_size, every region start on a 16-byte boundary); its
+ * segments lie back to back inside it: exactly the bytes appended to its
+ * files, in order.  Output rows (d_out_descs, d_out_results) are log-major, in
+ * descriptor order within a log, so a segment is a contiguous run of rows.
+ * d_out_descs are RPGPU_FMT_RP_DISK descriptors into d_out (ops = RPGPU_OP_CRC |
+ * RPGPU_OP_HDRCRC, the log's partition, length = size_bytes); d_out_results[r]
+ * is the input row with base_offset, header_crc, type and size_bytes as
+ * written.  index_first / index_count are unchanged: they still name the
+ * input index, whose offset column holds the produce-time offsets.  The
+ * output feeds rpgpu_run_device, rpgpu_kafka_serialize_device and, for ROLLED
+ * segments, rpgpu_segment_index_device without conversion (carrying index
+ * state into a continuing segment is the caller's: DESIGN.md §7).
+ * A segment row (rpgpu_append_segment) is opened at each roll, and for the
+ * continuing segment when the first eligible batch reaches it with left > 0.
+ * A ghost batch's file_pos is the position the next written batch takes.
+ *
+ * Plan, then run, on the same stream and scratch
+ * (rpgpu_append_scratch_bytes(n, nlogs) bytes).  The plan reads descriptors,
+ * result rows, codes and logs, never d_data; it fills every batch row, every
+ * log row and d_totals: [0] the smallest out_cap that holds every log, [1]
+ * the output rows, [2] the segment rows.  A log is written whole or not at
+ * all: if its bytes end past out_cap, its rows past rows_cap or its segment
+ * rows past seg_cap, the run sets its status to RPGPU_APPEND_NO_ROOM (a log
+ * without bytes, rows or segments needs no room for them); every other field
+ * is kept, they say what it needs, and nothing of such a log is written.  The
+ * run writes nothing outside the regions of OK logs and nothing at or past
+ * out_cap; d_out must not overlap d_data.  A plan may be run any number of
+ * times; every run sets the status of every log again.
+ *
+ * Hand vector: one log {next_offset 42, file_offset 0, max_segment_size 64},
+ * two wire batches (71 and 78 bytes; the first exhausts the segment, the
+ * second rolls):
+ *   in  00000000000000000000003b0000000002d00832e900000000000000000000000003
+ *       e800000000000003e800000000000000010002000000030000000112000000026b04
+ *       763100
+ *       0000000000000007000000420000000002d66127c600000000000100000000000007
+ *       d000000000000007d1ffffffffffffffffffffffffffff0000000210000000010476
+ *       32000e000202026b0100
+ *   out af809a44470000002a0000000000000001e93208d0000000000000e8030000000000
+ *       00e80300000000000001000000000000000200030000000100000012000000026b04
+ *       763100
+ *       8f4feff44e0000002b0000000000000001c62761d6000001000000d0070000000000
+ *       00d107000000000000ffffffffffffffffffffffffffff0200000010000000010476
+ *       32000e000202026b0100
+ *   rows {APPENDED, 0, base 42, pos 0, segment 0}, {APPENDED, 1, 43, 0, 1};
+ *   log {OK, 2 batches, 2 segments, last_offset 44, next_offset 45, 149 bytes};
+ *   segments {flags 0, first 0, count 1, base 42, pos 0, out 0, 71 bytes},
+ *            {ROLLED, first 1, count 1, base 43, pos 0, out 71, 78 bytes}. */
+#define RPGPU_APPEND_ROLL_FIRST 1u /* rpgpu_append_log.flags */
+typedef struct rpgpu_append_log {
+    int64_t next_offset;       /* offset the next batch takes (_idx)             */
+    uint64_t file_offset;      /* size of the active segment's file              */
+    uint64_t max_segment_size;
+    uint32_t flags;            /* RPGPU_APPEND_ROLL_FIRST                        */
+    uint32_t reserved;
+} rpgpu_append_log;            /* 32 bytes */
+
+enum rpgpu_append_action { RPGPU_APPEND_SKIPPED = 0, RPGPU_APPEND_APPENDED = 1, RPGPU_APPEND_GHOST = 2 };
+typedef struct rpgpu_append_batch { /* one per input descriptor */
+    int32_t action;            /* enum rpgpu_append_action                       */
+    uint32_t out_row;          /* row in d_out_descs / d_out_results; UINT32_MAX if none */
+    int64_t base_offset;
+    uint64_t file_pos;         /* start_physical_offset in its segment           */
+    uint32_t segment;          /* row in the segment table                       */
+    uint32_t reserved;
+} rpgpu_append_batch;          /* 32 bytes */
+
+enum rpgpu_append_status { RPGPU_APPEND_OK = 0, RPGPU_APPEND_NO_ROOM = 1, RPGPU_APPEND_BAD_CONFIG = 2 };
+typedef struct rpgpu_append_log_result { /* append_result (end_of_stream) plus bookkeeping */
+    int32_t status;            /* enum rpgpu_append_status                       */
+    uint32_t batches;          /* batches written                                */
+    uint32_t ghosts;
+    uint32_t segments;         /* segment rows                                   */
+    uint32_t first_row;        /* first output row                               */
+    uint32_t first_segment;    /* first segment row                              */
+    int64_t base_offset;       /* = rpgpu_append_log.next_offset                 */
+    int64_t last_offset;       /* INT64_MIN when nothing was eligible            */
+    int64_t next_offset;       /* _idx after the call                            */
+    uint64_t byte_size;
+    uint64_t out_offset;       /* the log's region in d_out                      */
+} rpgpu_append_log_result;     /* 64 bytes */
+
+#define RPGPU_APPEND_SEG_ROLLED 1u /* rpgpu_append_segment.flags: a new segment file */
+typedef struct rpgpu_append_segment {
+    uint32_t log;
+    uint32_t flags;            /* RPGPU_APPEND_SEG_ROLLED                        */
+    uint32_t first, count;     /* output rows; count 0: only ghosts reached it   */
+    int64_t base_offset;       /* _idx when the row was opened (ROLLED: the new
+                                  segment's base offset)                         */
+    uint64_t file_pos;         /* 0 when ROLLED, else file_offset                */
+    uint64_t out_offset;       /* its bytes in d_out                             */
+    uint64_t bytes;
+} rpgpu_append_segment;        /* 48 bytes */
+
+size_t rpgpu_append_scratch_bytes(uint32_t n, uint32_t nlogs);
+int32_t rpgpu_append_plan_device(rpgpu_ctx* ctx, const rpgpu_batch_desc* d_descs,
+                                 const rpgpu_batch_result* d_results, uint32_t n, const int32_t* d_codes,
+                                 const rpgpu_append_log* d_logs, uint32_t part_lo, uint32_t nlogs,
+                                 rpgpu_append_batch* d_batch_rows, rpgpu_append_log_result* d_log_results,
+                                 uint64_t* d_totals, void* d_scratch, void* hip_stream);
+int32_t rpgpu_append_run_device(rpgpu_ctx* ctx, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                const rpgpu_batch_result* d_results, uint32_t n, const rpgpu_append_log* d_logs,
+                                uint32_t part_lo, uint32_t nlogs, const rpgpu_append_batch* d_batch_rows,
+                                rpgpu_append_log_result* d_log_results, uint8_t* d_out, uint64_t out_cap,
+                                rpgpu_batch_desc* d_out_descs, rpgpu_batch_result* d_out_results, uint32_t rows_cap,
+                                rpgpu_append_segment* d_segments, uint32_t seg_cap, void* d_scratch,
+                                void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,23 @@ PP_RESPONSE_DTYPE = np.dtype([("first_range", "<u4"), ("range_count", "<u4")])
 PP_RESULT_DTYPE = np.dtype([("out_off", "<u8"), ("out_len", "<u8"), ("records", "<u4"), ("status", "<i4"),
                             ("bad_batch", "<u4"), ("reserved", "<u4")])
 assert PP_RANGE_DTYPE.itemsize == 24 and PP_RESPONSE_DTYPE.itemsize == 8 and PP_RESULT_DTYPE.itemsize == 32
+# log append (rpgpu_append_*)
+APPEND_ROLL_FIRST = 1  # rpgpu_append_log.flags
+APPEND_SKIPPED, APPEND_APPENDED, APPEND_GHOST = range(3)  # rpgpu_append_batch.action
+APPEND_OK, APPEND_NO_ROOM, APPEND_BAD_CONFIG = range(3)  # rpgpu_append_log_result.status
+APPEND_SEG_ROLLED = 1  # rpgpu_append_segment.flags
+APPEND_LOG_DTYPE = np.dtype([("next_offset", "<i8"), ("file_offset", "<u8"), ("max_segment_size", "<u8"),
+                             ("flags", "<u4"), ("reserved", "<u4")])
+APPEND_BATCH_DTYPE = np.dtype([("action", "<i4"), ("out_row", "<u4"), ("base_offset", "<i8"), ("file_pos", "<u8"),
+                               ("segment", "<u4"), ("reserved", "<u4")])
+APPEND_LOG_RESULT_DTYPE = np.dtype([("status", "<i4"), ("batches", "<u4"), ("ghosts", "<u4"), ("segments", "<u4"),
+                                    ("first_row", "<u4"), ("first_segment", "<u4"), ("base_offset", "<i8"),
+                                    ("last_offset", "<i8"), ("next_offset", "<i8"), ("byte_size", "<u8"),
+                                    ("out_offset", "<u8")])
+APPEND_SEGMENT_DTYPE = np.dtype([("log", "<u4"), ("flags", "<u4"), ("first", "<u4"), ("count", "<u4"),
+                                 ("base_offset", "<i8"), ("file_pos", "<u8"), ("out_offset", "<u8"), ("bytes", "<u8")])
+assert APPEND_LOG_DTYPE.itemsize == 32 and APPEND_BATCH_DTYPE.itemsize == 32
+assert APPEND_LOG_RESULT_DTYPE.itemsize == 64 and APPEND_SEGMENT_DTYPE.itemsize == 48
 INDEX_ENTRY_DTYPE = np.dtype([("relative_offset", "<u4"), ("relative_time", "<u4"), ("position", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 32 and SEGMENT_STATE_DTYPE.itemsize == 48 and INDEX_ENTRY_DTYPE.itemsize == 16
 assert INDEX_DTYPE.itemsize == 32 and RP_HEADER_DTYPE.itemsize == 61
@@ -310,6 +327,10 @@ def lib() -> C.CDLL:
              _vp, _vp, _vp, _vp)
         _sig(L.rpgpu_pp_fetch_run_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u64,
              _vp, _vp, _vp)
+        _sig(L.rpgpu_append_scratch_bytes, C.c_size_t, _u32, _u32)
+        _sig(L.rpgpu_append_plan_device, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_append_run_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u64,
+             _vp, _vp, _u32, _vp, _u32, _vp, _vp)
         _LIB = L
     return _LIB
 
@@ -348,4 +369,5 @@ EXPORTED = [
     "rpgpu_crc32_ranges_device", "rpgpu_crc32_extend", "rpgpu_legacy_scratch_bytes", "rpgpu_legacy_plan_device",
     "rpgpu_legacy_run_device", "rpgpu_convert_message_set", "rpgpu_legacy_kafka_error_code",
     "rpgpu_pp_fetch_scratch_bytes", "rpgpu_pp_fetch_plan_device", "rpgpu_pp_fetch_run_device",
+    "rpgpu_append_scratch_bytes", "rpgpu_append_plan_device", "rpgpu_append_run_device",
 ]

@@ -126,6 +126,17 @@ hipError_t launch_pp_fetch_run(const uint8_t* d_data, const rpgpu_batch_desc* d_
                                const rpgpu_pp_response* d_responses, uint32_t nresponses, uint8_t* d_out,
                                uint64_t out_cap, rpgpu_pp_result* d_out_results, void* d_scratch, uint32_t lane_max,
                                hipStream_t s);
+size_t append_scratch_bytes(uint32_t n, uint32_t nlogs);
+hipError_t launch_append_plan(const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_res, uint32_t n,
+                              const int32_t* d_codes, const rpgpu_append_log* d_logs, uint32_t part_lo,
+                              uint32_t nlogs, rpgpu_append_batch* d_rows, rpgpu_append_log_result* d_lres,
+                              uint64_t* d_totals, void* d_scratch, hipStream_t s);
+hipError_t launch_append_run(const uint8_t* d_data, const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_res,
+                             uint32_t n, uint32_t part_lo, uint32_t nlogs, const rpgpu_append_batch* d_rows,
+                             rpgpu_append_log_result* d_lres, uint8_t* d_out, uint64_t out_cap,
+                             rpgpu_batch_desc* d_out_descs, rpgpu_batch_result* d_out_res, uint32_t rows_cap,
+                             rpgpu_append_segment* d_segments, uint32_t seg_cap, void* d_scratch,
+                             const uint32_t* d_tables, hipStream_t s);
 }  // namespace rpgpu
 
 namespace {
@@ -524,6 +535,43 @@ int32_t rpgpu_pp_fetch_run_device(rpgpu_ctx* c, const uint8_t* d_data, const rpg
                                               d_responses, nresponses, d_out, out_cap, d_out_results, d_scratch,
                                               c->pp_lane_max, s);
     if (e != hipSuccess) return fail(c, e, "pandaproxy fetch run launch");
+    return RPGPU_OK;
+}
+
+size_t rpgpu_append_scratch_bytes(uint32_t n, uint32_t nlogs) { return rpgpu::append_scratch_bytes(n, nlogs); }
+
+int32_t rpgpu_append_plan_device(rpgpu_ctx* c, const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_results,
+                                 uint32_t n, const int32_t* d_codes, const rpgpu_append_log* d_logs, uint32_t part_lo,
+                                 uint32_t nlogs, rpgpu_append_batch* d_batch_rows,
+                                 rpgpu_append_log_result* d_log_results, uint64_t* d_totals, void* d_scratch,
+                                 void* hip_stream) {
+    // the sort key nlogs stands for "not appended": it must fit beside the logs
+    if (!c || !d_totals || nlogs == UINT32_MAX || (n && (!d_descs || !d_results || !d_batch_rows)) ||
+        (nlogs && (!d_logs || !d_log_results)) || ((n || nlogs) && !d_scratch))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_append_plan(d_descs, d_results, n, d_codes, d_logs, part_lo, nlogs, d_batch_rows,
+                                             d_log_results, d_totals, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "append plan launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_append_run_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                const rpgpu_batch_result* d_results, uint32_t n, const rpgpu_append_log* d_logs,
+                                uint32_t part_lo, uint32_t nlogs, const rpgpu_append_batch* d_batch_rows,
+                                rpgpu_append_log_result* d_log_results, uint8_t* d_out, uint64_t out_cap,
+                                rpgpu_batch_desc* d_out_descs, rpgpu_batch_result* d_out_results, uint32_t rows_cap,
+                                rpgpu_append_segment* d_segments, uint32_t seg_cap, void* d_scratch,
+                                void* hip_stream) {
+    if (!c || nlogs == UINT32_MAX || (n && (!d_data || !d_descs || !d_results || !d_batch_rows)) ||
+        (nlogs && (!d_logs || !d_log_results)) || ((n || nlogs) && !d_scratch) || (out_cap && !d_out) ||
+        (rows_cap && (!d_out_descs || !d_out_results)) || (seg_cap && !d_segments) || (n && d_data == d_out))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_append_run(d_data, d_descs, d_results, n, part_lo, nlogs, d_batch_rows,
+                                            d_log_results, d_out, out_cap, d_out_descs, d_out_results, rows_cap,
+                                            d_segments, seg_cap, d_scratch, c->d_tables, s);
+    if (e != hipSuccess) return fail(c, e, "append run launch");
     return RPGPU_OK;
 }
 

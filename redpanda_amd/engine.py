@@ -642,6 +642,97 @@ class Engine:
         return (d_out.cpu().numpy()[: out_cap + guard].copy(),
                 d_pres.cpu().numpy().view(abi.PP_RESULT_DTYPE)[:nq].copy())
 
+    def kafka_error_codes(self, results: np.ndarray, batch_max_bytes: int = 0) -> np.ndarray:
+        """rpgpu_kafka_error_codes_device over host result rows: one int32 code per batch."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        results = np.ascontiguousarray(results, dtype=abi.RESULT_DTYPE)
+        n = len(results)
+        d_res = torch.from_numpy(results.view(np.uint8).reshape(-1).copy() if n else np.zeros(64, np.uint8)).to(dev)
+        d_codes = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        rc = self._lib.rpgpu_kafka_error_codes_device(self._ctx, d_res.data_ptr(), n, batch_max_bytes,
+                                                      d_codes.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_kafka_error_codes_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return d_codes.cpu().numpy()[:n].copy()
+
+    def append_arena(self, data: np.ndarray, descs: np.ndarray, results: np.ndarray, logs: np.ndarray,
+                     part_lo: int = 0, codes: np.ndarray | None = None, out_cap: int | None = None,
+                     rows_cap: int | None = None, seg_cap: int | None = None, plans: int = 1, runs: int = 1,
+                     fill: int | None = None, guard: int = 0) -> dict:
+        """rpgpu_append_plan_device / rpgpu_append_run_device: the validated batches
+        of a host arena appended to the logs [part_lo, part_lo + len(logs)).
+        Returns host copies: out (out_cap bytes, the plan's total by default,
+        then `guard` more; pre-filled with `fill` when given, else zero),
+        rows (per descriptor), log_results, segments (seg_cap rows and one more),
+        out_descs and out_results (rows_cap rows and one more; the row tables are
+        pre-filled like out, so a caller sees what the run left alone), totals
+        (the plan's three) and the capacities used.  codes: the
+        int32 codes of rpgpu_kafka_error_codes_device, or None.  plans / runs:
+        how often each stage is enqueued."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        descs = np.ascontiguousarray(descs, dtype=abi.DESC_DTYPE)
+        results = np.ascontiguousarray(results, dtype=abi.RESULT_DTYPE)
+        logs = np.ascontiguousarray(logs, dtype=abi.APPEND_LOG_DTYPE)
+        n, nl = len(descs), len(logs)
+        if len(results) != n or (codes is not None and len(codes) != n):
+            raise ValueError("one result row (and one code) per descriptor")
+
+        def up(a):
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(64, np.uint8)).to(dev)
+
+        def rows(count, dtype, value=0):
+            return torch.full((max(count, 1) * dtype.itemsize,), value, dtype=torch.uint8, device=dev)
+
+        d_data = up(np.concatenate([data, np.zeros(abi.ARENA_TAIL_PAD, np.uint8)]))
+        d_descs, d_res, d_logs = up(descs), up(results), up(logs)
+        d_codes = None if codes is None else up(np.ascontiguousarray(codes, dtype=np.int32))
+        d_rows = rows(n, abi.APPEND_BATCH_DTYPE)
+        d_lres = rows(nl, abi.APPEND_LOG_RESULT_DTYPE)
+        d_tot = torch.zeros(3, dtype=torch.int64, device=dev)
+        d_scr = torch.zeros(max(int(self._lib.rpgpu_append_scratch_bytes(n, nl)), 1), dtype=torch.uint8, device=dev)
+        for _ in range(plans):
+            rc = self._lib.rpgpu_append_plan_device(self._ctx, d_descs.data_ptr(), d_res.data_ptr(), n,
+                                                    d_codes.data_ptr() if d_codes is not None else None,
+                                                    d_logs.data_ptr(), part_lo, nl, d_rows.data_ptr(),
+                                                    d_lres.data_ptr(), d_tot.data_ptr(), d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_append_plan_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        totals = d_tot.cpu().numpy().astype(np.uint64)
+        out_cap = int(totals[0]) if out_cap is None else out_cap
+        rows_cap = int(totals[1]) if rows_cap is None else rows_cap
+        seg_cap = int(totals[2]) if seg_cap is None else seg_cap
+        fillv = 0 if fill is None else fill
+        d_out = torch.full((max(out_cap + guard, 1),), fillv, dtype=torch.uint8, device=dev)
+        d_odescs = rows(rows_cap + 1, abi.DESC_DTYPE, fillv)
+        d_ores = rows(rows_cap + 1, abi.RESULT_DTYPE, fillv)
+        d_segs = rows(seg_cap + 1, abi.APPEND_SEGMENT_DTYPE, fillv)
+        for _ in range(runs):
+            rc = self._lib.rpgpu_append_run_device(self._ctx, d_data.data_ptr(), d_descs.data_ptr(), d_res.data_ptr(),
+                                                   n, d_logs.data_ptr(), part_lo, nl, d_rows.data_ptr(),
+                                                   d_lres.data_ptr(), d_out.data_ptr(), out_cap,
+                                                   d_odescs.data_ptr(), d_ores.data_ptr(), rows_cap,
+                                                   d_segs.data_ptr(), seg_cap, d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_append_run_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        # one row past each capacity comes back too: it must still hold the fill
+        return dict(out=d_out.cpu().numpy()[: out_cap + guard].copy(),
+                    rows=d_rows.cpu().numpy().view(abi.APPEND_BATCH_DTYPE)[:n].copy(),
+                    log_results=d_lres.cpu().numpy().view(abi.APPEND_LOG_RESULT_DTYPE)[:nl].copy(),
+                    segments=d_segs.cpu().numpy().view(abi.APPEND_SEGMENT_DTYPE)[:seg_cap + 1].copy(),
+                    out_descs=d_odescs.cpu().numpy().view(abi.DESC_DTYPE)[:rows_cap + 1].copy(),
+                    out_results=d_ores.cpu().numpy().view(abi.RESULT_DTYPE)[:rows_cap + 1].copy(),
+                    totals=totals, out_cap=out_cap, rows_cap=rows_cap, seg_cap=seg_cap)
+
     def batch_timequery(self, results: np.ndarray, index: np.ndarray, queries: np.ndarray) -> np.ndarray:
         """rpgpu_batch_timequery_device (storage::batch_timequery) per query."""
         import torch
