@@ -22,7 +22,7 @@ LIBRPGPU = PKG / "librpgpu.so"
 LIBRPGEN = PKG / "librpgen.so"
 
 RPGPU_SRCS = ["rpgpu_kernels.hip", "rpgpu_decomp.hip", "rpgpu_sets.hip", "rpgpu_index.hip", "rpgpu_summary.hip", "rpgpu_compact.hip", "rpgpu_compact_rw.hip", "rpgpu_fetch.hip", "rpgpu_compress.hip", "rpgpu_stamp.hip", "rpgpu_legacy.hip", "rpgpu_pp.hip", "rpgpu_append.hip", "rpgpu_abi.cpp", "rpgpu_tables.cpp"]
-RPGPU_HDRS = ["rpgpu_internal.h", "rpgpu_device.h", "rpgpu_walk.h", "rpgpu_copy.h", "rpgpu_legacy.h", "rpgpu_pp.h", "rpgpu_codec.h", "rpgpu_zstd.h", "rpgpu_zseq.h", "rpgpu_zblk.h", "rpgpu_wave.h", "rpgpu_inflate.h", "rpgpu_lz4c.h", "rpgpu_snappyc.h", "rpgpu_deflatec.h", "rpgpu_zstdc.h"]
+RPGPU_HDRS = ["rpgpu_internal.h", "rpgpu_launch.h", "rpgpu_device.h", "rpgpu_scan.h", "rpgpu_rewrite.h", "rpgpu_walk.h", "rpgpu_copy.h", "rpgpu_legacy.h", "rpgpu_pp.h", "rpgpu_codec.h", "rpgpu_zstd.h", "rpgpu_zseq.h", "rpgpu_zblk.h", "rpgpu_wave.h", "rpgpu_inflate.h", "rpgpu_lz4c.h", "rpgpu_snappyc.h", "rpgpu_deflatec.h", "rpgpu_zstdc.h"]
 RPGEN_SRCS = ["rpgen.cpp"]
 RPGEN_HDRS = ["rpgen.h"]
 
@@ -61,7 +61,8 @@ def build_rpgpu(force: bool = False) -> Path:
             list(ex.map(lambda so: _run(["hipcc", *flags, "-c", str(CSRC / so[0]), "-o", str(so[1])]),
                         zip(RPGPU_SRCS, objs)))
         tmp = LIBRPGPU.with_suffix(".so.tmp")
-        _run(["hipcc", f"--offload-arch={ARCH}", "-shared", *[str(o) for o in objs], "-o", str(tmp)])
+        # --no-undefined: a launcher whose definition drifted from rpgpu_launch.h fails here, not at load
+        _run(["hipcc", f"--offload-arch={ARCH}", "-shared", "-Wl,--no-undefined", *[str(o) for o in objs], "-o", str(tmp)])
         os.replace(tmp, LIBRPGPU)
     return LIBRPGPU
 

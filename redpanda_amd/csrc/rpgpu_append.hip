@@ -45,6 +45,8 @@
 // Known bound: one log is walked by one wave, so an arena whose
 // batches nearly all belong to one log is walked serially, 64 batches a step.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
+#include "rpgpu_scan.h"
 
 namespace rpgpu {
 namespace {
@@ -85,21 +87,9 @@ uint32_t sort_passes(uint32_t nlogs) {
     return (bits + 7) / 8;
 }
 
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t v, int s) {
-    const uint32_t lo = __shfl_up((uint32_t)v, s, 64), hi = __shfl_up((uint32_t)(v >> 32), s, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
     const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
     return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_scan64(uint64_t x, uint32_t l) {  // inclusive, wrapping
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint64_t t = shfl_up64(x, s);
-        if (l >= (uint32_t)s) x += t;
-    }
-    return x;
 }
 
 __global__ __launch_bounds__(256) void append_classify_kernel(const rpgpu_batch_desc* __restrict__ descs,
@@ -134,28 +124,10 @@ __global__ __launch_bounds__(256) void append_classify_kernel(const rpgpu_batch_
     }
 }
 
-// in-place exclusive scan of a[0, len) by one workgroup: a contiguous chunk per thread
-__global__ __launch_bounds__(kScanThreads) void append_scan_kernel(uint32_t* __restrict__ a, uint32_t len) {
-    __shared__ uint32_t part[kScanThreads];
-    const uint32_t t = threadIdx.x;
-    const uint64_t c = ((uint64_t)len + kScanThreads - 1) / kScanThreads;
-    const uint64_t lo = t * c < len ? t * c : len, hi = lo + c < len ? lo + c : len;
-    uint32_t s = 0;
-    for (uint64_t k = lo; k < hi; k++) s += a[k];
-    part[t] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < kScanThreads; off <<= 1) {
-        const uint32_t v = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - s;
-    for (uint64_t k = lo; k < hi; k++) {
-        const uint32_t v = a[k];
-        a[k] = run;
-        run += v;
-    }
+// in-place exclusive scan of a[0, len) by one workgroup
+__global__ __launch_bounds__(kScanBlock) void append_scan_kernel(uint32_t* a, uint32_t len) {
+    __shared__ uint32_t part[kScanBlock];
+    (void)array_scan_excl(a, a, len, part);
 }
 
 // item i of a pass's input order (pass 0: the descriptors' own order)
@@ -254,7 +226,7 @@ __global__ __launch_bounds__(256) void append_walk_kernel(const rpgpu_batch_desc
             w = (uint64_t)((int64_t)r.last_offset_delta + 1);
             sz = ghost ? 0 : (uint64_t)(uint32_t)r.size_bytes;
         }
-        const uint64_t W = wave_scan64(w, l), S = wave_scan64(sz, l);
+        const uint64_t W = wave_scan_incl(w, l), S = wave_scan_incl(sz, l);  // wrapping
         const uint64_t E = S - sz;  // bytes of this step in front of the batch
         const uint64_t wm = __ballot(live && !ghost);
         const uint64_t lanes_below = (1ull << l) - 1;
@@ -556,7 +528,7 @@ hipError_t launch_append_plan(const rpgpu_batch_desc* d_descs, const rpgpu_batch
         AP_CHECK();
     }
     if (nlogs == 0) return hipSuccess;
-    append_scan_kernel<<<1, kScanThreads, 0, s>>>(p.starts, nlogs + 1);
+    append_scan_kernel<<<1, kScanBlock, 0, s>>>(p.starts, nlogs + 1);
     AP_CHECK();
     const uint32_t passes = sort_passes(nlogs), nb = sort_blocks(n);
     const uint32_t* in = nullptr;
@@ -564,7 +536,7 @@ hipError_t launch_append_plan(const rpgpu_batch_desc* d_descs, const rpgpu_batch
         uint32_t* out = (k & 1) ? p.idx_b : p.idx_a;
         append_hist_kernel<<<nb, kSortBlock, 0, s>>>(p.key, in, n, 8 * k, nb, p.table);
         AP_CHECK();
-        append_scan_kernel<<<1, kScanThreads, 0, s>>>(p.table, nb * 256);
+        append_scan_kernel<<<1, kScanBlock, 0, s>>>(p.table, nb * 256);
         AP_CHECK();
         append_scatter_kernel<<<nb, kSortBlock, 0, s>>>(p.key, in, n, 8 * k, nb, p.table, out);
         AP_CHECK();

@@ -32,6 +32,7 @@
 // (storage/log_reader.cc:381-407), one lane per query over the batch's index
 // entries.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
 
 namespace rpgpu {
 

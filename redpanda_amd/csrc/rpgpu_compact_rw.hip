@@ -17,7 +17,8 @@
 //   validate_kernel       RECRC over the outputs: crc over the new body, then
 //                         header_crc (reset_size_checksum_metadata,
 //                         storage/parser_utils.cc:122-128); record walk, index
-//   compact_patch_kernel  stores both CRCs into the output headers
+//   recrc_patch_kernel    stores both CRCs into the output headers
+//                         (rpgpu_rewrite.h)
 //
 // The record walk is for_each_record's (model/record.h:668-691 over
 // record_utils.cc:93-176) on a batch that validated OK: sizes narrowed to
@@ -25,17 +26,10 @@
 // silent, every header of a record's count materialised (past the end of
 // input as (0, 0)) -- oracle/compact.c restates the same.
 #include "rpgpu_device.h"
+#include "rpgpu_rewrite.h"
+#include "rpgpu_scan.h"
 
 namespace rpgpu {
-
-hipError_t launch_block_scan(uint64_t* block_sum, uint32_t nb, uint64_t* total, hipStream_t s);
-hipError_t launch_plan(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                       uint64_t* d_index_used, void* d_scratch, hipStream_t s);
-hipError_t launch_run(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                      rpgpu_batch_result* d_res, rpgpu_record_index* d_index, uint64_t index_cap,
-                      const void* d_scratch, const uint32_t* d_tables, int grid, hipStream_t s,
-                      const Overlap* ov);
-size_t validate_scratch_bytes(uint32_t n);
 
 namespace {
 constexpr uint16_t kTxBit = 0x10, kControlBit = 0x20, kAppendTimeBit = 0x08;
@@ -222,26 +216,10 @@ __global__ __launch_bounds__(kScanBlock) void compact_plan_kernel(
         }
         meta[i] = m;
     }
-    const uint32_t l = lane_id();
-    uint64_t x = sz;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)x, s, 64), hi = __shfl_up((uint32_t)(x >> 32), s, 64);
-        if (l >= (uint32_t)s) x += ((uint64_t)hi << 32) | lo;
-    }
-    const uint32_t wv = threadIdx.x >> 6;
-    if (l == 63) wsum[wv] = x;
-    __syncthreads();
-    uint64_t wbase = 0;
-    for (uint32_t k = 0; k < wv; k++) wbase += wsum[k];
+    const uint64_t first = block_scan_excl(sz, wsum, block_sum);
     if (i < n) {
         slot[i] = sz;
-        local[i] = wbase + x - sz;
-    }
-    if (threadIdx.x == kScanBlock - 1) {
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < kScanBlock / 64; k++) tot += wsum[k];
-        block_sum[blockIdx.x] = tot;
+        local[i] = first;
     }
 }
 
@@ -273,15 +251,6 @@ struct WaveOut {
     }
 };
 
-__device__ __forceinline__ uint64_t hfield_rw(const uint8_t* p, int off, int nb, bool be) {
-    uint64_t v = 0;
-    for (int k = 0; k < nb; k++) v = be ? (v << 8) | p[off + k] : v | ((uint64_t)p[off + k] << (8 * k));
-    return v;
-}
-__device__ __forceinline__ void put_le_rw(uint8_t* o, int off, uint64_t v, int nb) {
-    for (int k = 0; k < nb; k++) o[off + k] = (uint8_t)(v >> (8 * k));
-}
-
 __global__ __launch_bounds__(256) void compact_write_kernel(
     const rpgpu_batch_desc* __restrict__ descs, const rpgpu_batch_result* __restrict__ res, uint32_t n,
     const uint8_t* __restrict__ data, const uint8_t* __restrict__ keep, const uint64_t* __restrict__ slot,
@@ -294,8 +263,8 @@ __global__ __launch_bounds__(256) void compact_write_kernel(
          i += nw) {
         const RwMeta m = meta[i];
         const rpgpu_batch_desc d = descs[i];
-        const uint64_t off = block_base[i / kScanBlock] + local[i];
         const uint64_t sz = slot[i];
+        const uint64_t off = slot_offset(block_base, local, i);
         int32_t action = m.action;
         const bool emit = sz != 0 && off + sz <= out_cap;
         if (sz != 0 && !emit) action = RPGPU_COMPACT_SKIPPED;  // caller's buffer below the plan
@@ -357,19 +326,19 @@ __global__ __launch_bounds__(256) void compact_write_kernel(
                 // the output header, on-disk layout (storage/parser.cc:40-80);
                 // crc / header_crc come from the RECRC validation
                 const bool be = d.format == RPGPU_FMT_KAFKA_WIRE;
-                put_le_rw(o, 0, 0, 4);
-                put_le_rw(o, 4, out_len, 4);
-                put_le_rw(o, 8, (uint64_t)r.base_offset, 8);
+                put_le(o, 0, 0, 4);
+                put_le(o, 4, out_len, 4);
+                put_le(o, 8, (uint64_t)r.base_offset, 8);
                 o[16] = (uint8_t)r.type;
-                put_le_rw(o, 17, 0, 4);
-                put_le_rw(o, 21, m.attrs, 2);
-                put_le_rw(o, 23, (uint32_t)r.last_offset_delta, 4);
-                put_le_rw(o, 27, (uint64_t)m.first_ts, 8);
-                put_le_rw(o, 35, (uint64_t)m.max_ts, 8);
-                put_le_rw(o, 43, hfield_rw(p, 43, 8, be), 8);
-                put_le_rw(o, 51, hfield_rw(p, 51, 2, be), 2);
-                put_le_rw(o, 53, hfield_rw(p, 53, 4, be), 4);
-                put_le_rw(o, 57, (uint32_t)m.record_count, 4);
+                put_le(o, 17, 0, 4);
+                put_le(o, 21, m.attrs, 2);
+                put_le(o, 23, (uint32_t)r.last_offset_delta, 4);
+                put_le(o, 27, (uint64_t)m.first_ts, 8);
+                put_le(o, 35, (uint64_t)m.max_ts, 8);
+                put_le(o, 43, hdr_field(p, 43, 8, be), 8);
+                put_le(o, 51, hdr_field(p, 51, 2, be), 2);
+                put_le(o, 53, hdr_field(p, 53, 4, be), 4);
+                put_le(o, 57, (uint32_t)m.record_count, 4);
             }
         }
         if (lane == 0) {
@@ -381,29 +350,12 @@ __global__ __launch_bounds__(256) void compact_write_kernel(
             c.removed = action == RPGPU_COMPACT_SKIPPED ? 0u : m.removed;
             c.reserved = 0;
             cres[i] = c;
-            rpgpu_batch_desc od;
-            od.offset = off;
-            od.length = (uint32_t)out_len;
-            od.partition = d.partition;
-            od.format = RPGPU_FMT_RP_DISK;
-            od.ops = emit ? (uint8_t)(RPGPU_OP_CRC | RPGPU_OP_HDRCRC | RPGPU_OP_RECRC |
-                                      (d.ops & (RPGPU_OP_PARSE | RPGPU_OP_INDEX)))
-                          : (uint8_t)0;
-            od.flags = 0;
-            od.reserved = 0;
-            out_descs[i] = od;
+            out_descs[i] = out_desc(off, (uint32_t)out_len, d.partition,
+                                    emit ? (uint8_t)(RPGPU_OP_CRC | RPGPU_OP_HDRCRC | RPGPU_OP_RECRC |
+                                                     (d.ops & (RPGPU_OP_PARSE | RPGPU_OP_INDEX)))
+                                         : (uint8_t)0);
         }
     }
-}
-
-__global__ __launch_bounds__(256) void compact_patch_kernel(const rpgpu_compact_result* __restrict__ cres,
-                                                            const rpgpu_batch_result* __restrict__ vres2,
-                                                            uint32_t n, uint8_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || cres[i].out_len == 0) return;
-    uint8_t* o = out + cres[i].out_offset;
-    put_le_rw(o, 0, vres2[i].header_crc, 4);
-    put_le_rw(o, 17, vres2[i].crc, 4);
 }
 
 hipError_t launch_compact_rw_plan(const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
@@ -432,12 +384,8 @@ hipError_t launch_compact_rw_run(const uint8_t* d_data, const rpgpu_batch_desc* 
                                                          p.block_sum, p.meta, d_cres, d_out, out_cap, d_out_descs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if ((e = launch_plan(d_out_descs, n, d_out, d_out_index_used, p.vscratch, s)) != hipSuccess) return e;
-    if ((e = launch_run(d_out_descs, n, d_out, d_out_res, d_out_index, out_index_cap, p.vscratch, d_tables, grid, s,
-                        nullptr)) != hipSuccess)
-        return e;
-    compact_patch_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_cres, d_out_res, n, d_out);
-    return hipGetLastError();
+    return launch_revalidate(d_out_descs, n, d_out, d_cres, d_out_res, d_out_index, out_index_cap, d_out_index_used,
+                             p.vscratch, d_tables, grid, s);
 }
 
 }  // namespace rpgpu

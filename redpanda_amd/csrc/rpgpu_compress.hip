@@ -18,10 +18,12 @@
 //                         block's "clear" is a counter increment
 //   validate_kernel       over the compressed batches with RPGPU_OP_RECRC: the
 //                         Kafka CRC of the payload, then the header CRC
-//   compress_patch_kernel stores both CRCs into the headers
+//   recrc_patch_kernel    stores both CRCs into the headers (rpgpu_rewrite.h)
 // A batch is compressed when it validated OK and is uncompressed (codec 0);
 // its result otherwise reads RPGPU_V_SKIPPED.
 #include "rpgpu_device.h"
+#include "rpgpu_rewrite.h"
+#include "rpgpu_scan.h"
 #include "rpgpu_codec.h"
 #include "rpgpu_lz4c.h"
 #include "rpgpu_snappyc.h"
@@ -29,15 +31,6 @@
 #include "rpgpu_zstdc.h"
 
 namespace rpgpu {
-
-hipError_t launch_block_scan(uint64_t* block_sum, uint32_t nb, uint64_t* total, hipStream_t s);
-hipError_t launch_plan(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                       uint64_t* d_index_used, void* d_scratch, hipStream_t s);
-hipError_t launch_run(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                      rpgpu_batch_result* d_res, rpgpu_record_index* d_index, uint64_t index_cap,
-                      const void* d_scratch, const uint32_t* d_tables, int grid, hipStream_t s,
-                      const Overlap* ov);
-size_t validate_scratch_bytes(uint32_t n);
 
 namespace {
 constexpr uint32_t kCompLanes = 131072, kEntropyLanes = 32768;
@@ -102,36 +95,11 @@ __global__ __launch_bounds__(kScanBlock) void compress_caps_kernel(const rpgpu_b
             sz = (kHeaderSize + comp_bound(codec, (uint64_t)(uint32_t)v.size_bytes - kHeaderSize) + kCompSlack + 15) &
                  ~(uint64_t)15;
     }
-    const uint32_t l = lane_id();
-    uint64_t x = sz;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)x, s, 64), hi = __shfl_up((uint32_t)(x >> 32), s, 64);
-        if (l >= (uint32_t)s) x += ((uint64_t)hi << 32) | lo;
-    }
-    const uint32_t wv = threadIdx.x >> 6;
-    if (l == 63) wsum[wv] = x;
-    __syncthreads();
-    uint64_t wbase = 0;
-    for (uint32_t k = 0; k < wv; k++) wbase += wsum[k];
+    const uint64_t first = block_scan_excl(sz, wsum, block_sum);
     if (i < n) {
         slot[i] = sz;
-        local[i] = wbase + x - sz;
+        local[i] = first;
     }
-    if (threadIdx.x == kScanBlock - 1) {
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < kScanBlock / 64; k++) tot += wsum[k];
-        block_sum[blockIdx.x] = tot;
-    }
-}
-
-__device__ __forceinline__ uint64_t hdr_field_c(const uint8_t* p, int off, int nb, bool be) {
-    uint64_t v = 0;
-    for (int k = 0; k < nb; k++) v = be ? (v << 8) | p[off + k] : v | ((uint64_t)p[off + k] << (8 * k));
-    return v;
-}
-__device__ __forceinline__ void put_le_c(uint8_t* o, int off, uint64_t v, int nb) {
-    for (int k = 0; k < nb; k++) o[off + k] = (uint8_t)(v >> (8 * k));
 }
 
 template <uint32_t CODEC>
@@ -153,7 +121,7 @@ __global__ __launch_bounds__(256) void compress_lane_kernel(
         const rpgpu_batch_desc d = descs[i];
         const rpgpu_batch_result v = vres[i];
         const uint64_t sz = slot[i];
-        const uint64_t off = block_base[i / kScanBlock] + local[i];
+        const uint64_t off = slot_offset(block_base, local, i);
         int32_t verdict = RPGPU_V_SKIPPED;
         uint64_t len = 0;
         uint8_t ops = 0;
@@ -188,19 +156,7 @@ __global__ __launch_bounds__(256) void compress_lane_kernel(
                 // the header of compress_batch (parser_utils.cc:107-113), on-disk
                 // layout; crc / header_crc follow from the RECRC validation
                 const bool be = d.format == RPGPU_FMT_KAFKA_WIRE;
-                put_le_c(o, 0, 0, 4);
-                put_le_c(o, 4, kHeaderSize + len, 4);
-                put_le_c(o, 8, be ? hdr_field_c(p, 0, 8, true) : hdr_field_c(p, 8, 8, false), 8);
-                o[16] = be ? (uint8_t)1 : p[16];
-                put_le_c(o, 17, 0, 4);
-                put_le_c(o, 21, (hdr_field_c(p, 21, 2, be) & ~(uint64_t)7) | CODEC, 2);  // attrs |= c
-                put_le_c(o, 23, hdr_field_c(p, 23, 4, be), 4);
-                put_le_c(o, 27, hdr_field_c(p, 27, 8, be), 8);
-                put_le_c(o, 35, hdr_field_c(p, 35, 8, be), 8);
-                put_le_c(o, 43, hdr_field_c(p, 43, 8, be), 8);
-                put_le_c(o, 51, hdr_field_c(p, 51, 2, be), 2);
-                put_le_c(o, 53, hdr_field_c(p, 53, 4, be), 4);
-                put_le_c(o, 57, hdr_field_c(p, 57, 4, be), 4);
+                RPGPU_WRITE_DISK_HEADER_FROM(o, p, be, CODEC, kHeaderSize + len);  // attrs |= c
                 verdict = RPGPU_V_OK;
                 ops = RPGPU_OP_CRC | RPGPU_OP_HDRCRC | RPGPU_OP_RECRC;
             }
@@ -212,26 +168,8 @@ __global__ __launch_bounds__(256) void compress_lane_kernel(
         r.out_len = len;
         r.out_cap = sz;
         cres[i] = r;
-        rpgpu_batch_desc od;
-        od.offset = off;
-        od.length = ops ? (uint32_t)(kHeaderSize + len) : 0u;
-        od.partition = d.partition;
-        od.format = RPGPU_FMT_RP_DISK;
-        od.ops = ops;
-        od.flags = 0;
-        od.reserved = 0;
-        out_descs[i] = od;
+        out_descs[i] = out_desc(off, ops ? (uint32_t)(kHeaderSize + len) : 0u, d.partition, ops);
     }
-}
-
-__global__ __launch_bounds__(256) void compress_patch_kernel(const rpgpu_decomp_result* __restrict__ cres,
-                                                             const rpgpu_batch_result* __restrict__ vres2, uint32_t n,
-                                                             uint8_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || cres[i].verdict != RPGPU_V_OK) return;
-    uint8_t* o = out + cres[i].out_offset;
-    put_le_c(o, 0, vres2[i].header_crc, 4);
-    put_le_c(o, 17, vres2[i].crc, 4);
 }
 
 hipError_t launch_compress_plan(const rpgpu_batch_result* d_vres, uint32_t n, uint32_t codec, uint64_t* d_out_bytes,
@@ -266,12 +204,8 @@ hipError_t launch_compress_run(const rpgpu_batch_desc* d_descs, uint32_t n, cons
     else RPGPU_COMPRESS_LAUNCH(4);
 #undef RPGPU_COMPRESS_LAUNCH
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = launch_plan(d_out_descs, n, d_out, nullptr, p.vscratch, s)) != hipSuccess) return e;
-    if ((e = launch_run(d_out_descs, n, d_out, d_vres2, nullptr, 0, p.vscratch, d_tables, grid, s, nullptr)) !=
-        hipSuccess)
-        return e;
-    compress_patch_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_cres, d_vres2, n, d_out);
-    return hipGetLastError();
+    // no index: the compressed records are not walked
+    return launch_revalidate(d_out_descs, n, d_out, d_cres, d_vres2, nullptr, 0, nullptr, p.vscratch, d_tables, grid, s);
 }
 
 }  // namespace rpgpu

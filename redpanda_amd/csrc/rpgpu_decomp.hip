@@ -35,8 +35,11 @@
 //   validate_kernel      over the rewritten batches with RPGPU_OP_RECRC: the
 //                        Kafka CRC of the decompressed body, then the header
 //                        CRC over the header carrying it; record walk; index
-//   decomp_patch_kernel  stores both CRCs into the rewritten headers
+//   recrc_patch_kernel   stores both CRCs into the rewritten headers
+//                        (rpgpu_rewrite.h)
 #include "rpgpu_device.h"  // before rpgpu_codec.h: HIP attributes
+#include "rpgpu_rewrite.h"
+#include "rpgpu_scan.h"
 #include "rpgpu_codec.h"
 #include "rpgpu_zstd.h"
 #include "rpgpu_zseq.h"
@@ -45,15 +48,6 @@
 #include "rpgpu_inflate.h"
 
 namespace rpgpu {
-
-hipError_t launch_block_scan(uint64_t* block_sum, uint32_t nb, uint64_t* total, hipStream_t s);
-hipError_t launch_plan(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                       uint64_t* d_index_used, void* d_scratch, hipStream_t s);
-hipError_t launch_run(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                      rpgpu_batch_result* d_res, rpgpu_record_index* d_index, uint64_t index_cap,
-                      const void* d_scratch, const uint32_t* d_tables, int grid, hipStream_t s,
-                      const Overlap* ov);
-size_t validate_scratch_bytes(uint32_t n);
 
 namespace {
 // wave decoders in flight: 8 per CU (the zstd workspace takes ~19 KB of the
@@ -286,6 +280,15 @@ __global__ __launch_bounds__(256) void gzip_bound_kernel(const rpgpu_batch_desc*
     }
 }
 
+// what decomp_caps_kernel scans per batch: the output slot, and the parts of a
+// split body (LZ4's in the low, snappy's in the high 32 bits)
+struct SlotParts {
+    uint64_t slot, parts;
+};
+__device__ __forceinline__ SlotParts operator+(SlotParts a, SlotParts b) { return {a.slot + b.slot, a.parts + b.parts}; }
+__device__ __forceinline__ SlotParts operator-(SlotParts a, SlotParts b) { return {a.slot - b.slot, a.parts - b.parts}; }
+__device__ __forceinline__ SlotParts shfl_up(SlotParts x, int s) { return {shfl_up(x.slot, s), shfl_up(x.parts, s)}; }
+
 // output slot per batch + exclusive scan within blocks of kScanBlock batches
 __global__ __launch_bounds__(kScanBlock) void decomp_caps_kernel(
     const rpgpu_batch_desc* __restrict__ descs, uint32_t n, const uint8_t* __restrict__ data,
@@ -293,8 +296,7 @@ __global__ __launch_bounds__(kScanBlock) void decomp_caps_kernel(
     uint64_t* __restrict__ block_sum, uint64_t max_decoded, uint32_t* __restrict__ wcount,
     uint32_t* __restrict__ wlist, uint32_t* __restrict__ sfirst, uint32_t* __restrict__ scount,
     SplitPart* __restrict__ parts, uint32_t pcap) {
-    __shared__ uint64_t wsum[kScanBlock / 64];
-    __shared__ uint64_t psum[kScanBlock / 64];
+    __shared__ SlotParts wsum[kScanBlock / 64];
     __shared__ uint32_t pbase[2];
     const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
     uint64_t sz = 0, need = 0;
@@ -335,47 +337,27 @@ __global__ __launch_bounds__(kScanBlock) void decomp_caps_kernel(
             np = codec == 3 ? rpcodec::lz4f_split(b, body, half, none) : rpcodec::snappy_java_split(b, body, half, none);
         }
     }
-    // exclusive scans within the workgroup: output slots, and the parts of
-    // both codecs (LZ4 in the low, snappy in the high 32 bits)
-    const uint64_t span = sz;
-    const uint64_t pspan = codec == 3 ? (uint64_t)np : ((uint64_t)np << 32);
-    const uint32_t l = lane_id();
-    uint64_t x = span, y = pspan;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t lo = __shfl_up((uint32_t)x, s, 64), hi = __shfl_up((uint32_t)(x >> 32), s, 64);
-        const uint32_t plo = __shfl_up((uint32_t)y, s, 64), phi = __shfl_up((uint32_t)(y >> 32), s, 64);
-        if (l >= (uint32_t)s) {
-            x += ((uint64_t)hi << 32) | lo;
-            y += ((uint64_t)phi << 32) | plo;
-        }
-    }
-    const uint32_t wv = threadIdx.x >> 6;
-    if (l == 63) {
-        wsum[wv] = x;
-        psum[wv] = y;
-    }
-    __syncthreads();
-    uint64_t wbase = 0, pwbase = 0;
-    for (uint32_t k = 0; k < wv; k++) {
-        wbase += wsum[k];
-        pwbase += psum[k];
-    }
+    // exclusive scans within the workgroup, side by side under one barrier:
+    // output slots, and the parts of both codecs
+    const SlotParts span = {sz, codec == 3 ? (uint64_t)np : ((uint64_t)np << 32)};
+    const SlotParts first = block_scan_excl(span, wsum);
     if (threadIdx.x == kScanBlock - 1) {
         // one reservation per codec per workgroup (a CAS per batch serialised
         // thousands of split batches: 42 ms of C5's plan)
-        const uint64_t tot = pwbase + y;
+        const uint64_t tot = first.parts + span.parts;
         pbase[0] = (uint32_t)tot ? atomicAdd(wcount + 2, (uint32_t)tot) : 0u;
         pbase[1] = (uint32_t)(tot >> 32) ? atomicAdd(wcount + 3, (uint32_t)(tot >> 32)) : 0u;
+        block_sum[blockIdx.x] = first.slot + span.slot;
     }
     __syncthreads();
+    const uint32_t l = lane_id();
     uint32_t sc = 0;  // the parts this batch was split into (0: decoded whole)
     if (i < n) {
         slot[i] = over ? (kOverCeiling | need) : sz;
-        local[i] = wbase + x - span;
+        local[i] = first.slot;
         uint32_t sf = 0;
         if (np) {
-            const uint64_t pe = pwbase + y - pspan;  // exclusive prefix within the workgroup
+            const uint64_t pe = first.parts;  // exclusive prefix within the workgroup
             const uint32_t k0 = (codec == 3 ? pbase[0] + (uint32_t)pe : pbase[1] + (uint32_t)(pe >> 32));
             SplitPart* const pp = parts + (codec == 3 ? 0 : half);
             if ((uint64_t)k0 + np <= half) {
@@ -438,21 +420,6 @@ __global__ __launch_bounds__(kScanBlock) void decomp_caps_kernel(
         zb = (uint32_t)__shfl(zb, __builtin_ctzll(zm), 64);
         if (zl) wlist[2 * (size_t)n + zb + (uint32_t)__builtin_popcountll(zm & ((1ull << l) - 1))] = i;
     }
-    if (threadIdx.x == kScanBlock - 1) {
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < kScanBlock / 64; k++) tot += wsum[k];
-        block_sum[blockIdx.x] = tot;
-    }
-}
-
-// header field of the input batch: big-endian on the wire, little-endian on disk
-__device__ __forceinline__ uint64_t hdr_field(const uint8_t* p, int off, int nb, bool be) {
-    uint64_t v = 0;
-    for (int k = 0; k < nb; k++) v = be ? (v << 8) | p[off + k] : v | ((uint64_t)p[off + k] << (8 * k));
-    return v;
-}
-__device__ __forceinline__ void put_le(uint8_t* o, int off, uint64_t v, int nb) {
-    for (int k = 0; k < nb; k++) o[off + k] = (uint8_t)(v >> (8 * k));
 }
 
 // the batch's result, rewritten header and rewritten descriptor
@@ -469,19 +436,7 @@ __device__ __forceinline__ void finish_batch(uint32_t i, const rpgpu_batch_desc&
         const uint8_t* p = data + d.offset;
         uint8_t* o = out + off;
         const bool be = d.format == RPGPU_FMT_KAFKA_WIRE;
-        put_le(o, 0, 0, 4);
-        put_le(o, 4, kHeaderSize + len, 4);
-        put_le(o, 8, be ? hdr_field(p, 0, 8, true) : hdr_field(p, 8, 8, false), 8);
-        o[16] = be ? (uint8_t)1 : p[16];  // raft_data on produce
-        put_le(o, 17, 0, 4);
-        put_le(o, 21, hdr_field(p, 21, 2, be) & ~(uint64_t)7, 2);
-        put_le(o, 23, hdr_field(p, 23, 4, be), 4);
-        put_le(o, 27, hdr_field(p, 27, 8, be), 8);
-        put_le(o, 35, hdr_field(p, 35, 8, be), 8);
-        put_le(o, 43, hdr_field(p, 43, 8, be), 8);
-        put_le(o, 51, hdr_field(p, 51, 2, be), 2);
-        put_le(o, 53, hdr_field(p, 53, 4, be), 4);
-        put_le(o, 57, hdr_field(p, 57, 4, be), 4);
+        RPGPU_WRITE_DISK_HEADER_FROM(o, p, be, 0, kHeaderSize + len);
         ops = RPGPU_OP_CRC | RPGPU_OP_HDRCRC | RPGPU_OP_RECRC | (d.ops & (RPGPU_OP_PARSE | RPGPU_OP_INDEX));
     }
     rpgpu_decomp_result r;
@@ -491,15 +446,7 @@ __device__ __forceinline__ void finish_batch(uint32_t i, const rpgpu_batch_desc&
     r.out_len = len;
     r.out_cap = sz;
     dres[i] = r;
-    rpgpu_batch_desc od;
-    od.offset = off;
-    od.length = ops ? (uint32_t)(kHeaderSize + len) : 0u;
-    od.partition = d.partition;
-    od.format = RPGPU_FMT_RP_DISK;
-    od.ops = ops;
-    od.flags = 0;
-    od.reserved = 0;
-    out_descs[i] = od;
+    out_descs[i] = out_desc(off, ops ? (uint32_t)(kHeaderSize + len) : 0u, d.partition, ops);
 }
 
 // the batch's output slot, or the verdict that it gets none (len: the
@@ -558,7 +505,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RPGPU_LANE_
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < c2 + c3; g += lanes) {
         const uint32_t i = g < c2 ? list[n - 1 - g] : list[g - c2];
         uint64_t sz = slot[i];
-        const uint64_t off = block_base[i / kScanBlock] + local[i];
+        const uint64_t off = slot_offset(block_base, local, i);
         int32_t verdict = RPGPU_V_SKIPPED;
         uint64_t len = 0;
         {
@@ -586,7 +533,7 @@ __global__ __launch_bounds__(256) void skip_kernel(const rpgpu_batch_desc* __res
     const rpgpu_batch_desc d = descs[i];
     const rpgpu_batch_result v = vres[i];
     if (decomp_wanted(d, v)) return;
-    finish_batch(i, d, v, block_base[i / kScanBlock] + local[i], slot[i], RPGPU_V_SKIPPED, 0, data, out, dres,
+    finish_batch(i, d, v, slot_offset(block_base, local, i), slot[i], RPGPU_V_SKIPPED, 0, data, out, dres,
                  out_descs);
 }
 
@@ -629,7 +576,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RPGPU_WS_WA
         const rpgpu_batch_result v = vres[i];
         uint64_t sz = slot[i];
         if (!decomp_wanted(d, v) || v.codec != FAM || wave_owned(d, v, sz)) continue;
-        const uint64_t off = block_base[i / kScanBlock] + local[i];
+        const uint64_t off = slot_offset(block_base, local, i);
         int32_t verdict = RPGPU_V_SKIPPED;
         uint64_t len = 0;
         if (plan_slot(sz, off, out_cap, verdict, len)) {
@@ -679,7 +626,7 @@ __global__ __launch_bounds__(256) void zstd_ring_kernel(
         const rpgpu_batch_desc d = descs[i];
         const rpgpu_batch_result v = vres[i];
         uint64_t sz = slot[i];
-        const uint64_t off = block_base[i / kScanBlock] + local[i];
+        const uint64_t off = slot_offset(block_base, local, i);
         uint64_t len = 0;
         rpzstd::DirectEmit em;
         const int32_t verdict = rpzstd::uncompress<true>(em, data + d.offset + kHeaderSize, body_len(v),
@@ -857,7 +804,7 @@ __global__ __launch_bounds__(64) void zblk_exec_kernel(
     const rpgpu_batch_desc d = descs[i];
     const rpgpu_batch_result v = vres[i];
     uint64_t sz = slot[i];
-    const uint64_t off = block_base[i / kScanBlock] + local[i];
+    const uint64_t off = slot_offset(block_base, local, i);
     int32_t verdict = RPGPU_V_SKIPPED;
     uint64_t len = 0;
     if (plan_slot(sz, off, out_cap, verdict, len)) {
@@ -957,7 +904,7 @@ __global__ __launch_bounds__(64) void decomp_wave_kernel(
         // split bodies whose parts did not bear the plan out (split_finish_kernel) --
         // those may be as small as the split threshold, below the wave size
         if (!decomp_wanted(d, v) || !in_family(FAM, v.codec)) continue;
-        const uint64_t off = block_base[i / kScanBlock] + local[i];
+        const uint64_t off = slot_offset(block_base, local, i);
         int32_t verdict = RPGPU_V_SKIPPED;
         uint64_t len = 0;
         if (plan_slot(sz, off, out_cap, verdict, len)) {
@@ -986,7 +933,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RPGPU_LANE_
     for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < c2 + c3; g += lanes) {
         const SplitPart t = parts[g < c2 ? half + g : g - c2];
         if (t.kind == kSkipPart) continue;
-        const uint64_t off = block_base[t.batch / kScanBlock] + local[t.batch];
+        const uint64_t off = slot_offset(block_base, local, t.batch);
         int32_t r = -2;
         if (off + slot[t.batch] <= out_cap) {
             const uint8_t* in = data + descs[t.batch].offset + kHeaderSize + t.in_off;
@@ -1012,7 +959,7 @@ __global__ __launch_bounds__(256) void split_finish_kernel(
     const rpgpu_batch_desc d = descs[i];
     const rpgpu_batch_result v = vres[i];
     uint64_t sz = slot[i];
-    const uint64_t off = block_base[i / kScanBlock] + local[i];
+    const uint64_t off = slot_offset(block_base, local, i);
     int32_t verdict = RPGPU_V_OK;
     uint64_t len = 0;
     if (!plan_slot(sz, off, out_cap, verdict, len)) {
@@ -1026,17 +973,6 @@ __global__ __launch_bounds__(256) void split_finish_kernel(
         finish_batch(i, d, v, off, sz, verdict, len, data, out, dres, out_descs);
     else
         wlist[n + atomicAdd(lz_count, 1u)] = i;
-}
-
-// stores the CRCs the validation of the rewritten batches computed
-__global__ __launch_bounds__(256) void decomp_patch_kernel(const rpgpu_decomp_result* __restrict__ dres,
-                                                           const rpgpu_batch_result* __restrict__ vres2, uint32_t n,
-                                                           uint8_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || dres[i].verdict != RPGPU_V_OK) return;
-    uint8_t* o = out + dres[i].out_offset;
-    put_le(o, 0, vres2[i].header_crc, 4);
-    put_le(o, 17, vres2[i].crc, 4);
 }
 
 // scalar mirror (rpgpu_uncompress): the bound in one lane, the decode in one
@@ -1277,14 +1213,8 @@ hipError_t launch_decomp_run(const rpgpu_batch_desc* d_descs, uint32_t n, const 
         if ((e = hipStreamWaitEvent(s, ds->join2, 0)) != hipSuccess) return e;
 #endif
     }
-    if ((e = launch_plan(d_out_descs, n, d_out, d_index_used, p.vscratch, s)) != hipSuccess) return e;
-    // no chunked walk overlap here: the rewritten arena is walked in one launch (16
-    // chunks measured slower on C3: 103 vs 95 ms per step)
-    if ((e = launch_run(d_out_descs, n, d_out, d_vres2, d_index, index_cap, p.vscratch, d_tables, grid, s, nullptr)) !=
-        hipSuccess)
-        return e;
-    decomp_patch_kernel<<<nblk, 256, 0, s>>>(d_dres, d_vres2, n, d_out);
-    return hipGetLastError();
+    return launch_revalidate(d_out_descs, n, d_out, d_dres, d_vres2, d_index, index_cap, d_index_used, p.vscratch,
+                             d_tables, grid, s);
 }
 
 hipError_t launch_uncompress_bound(uint32_t codec, const uint8_t* d_in, uint64_t n, uint64_t* d_res,

@@ -18,6 +18,8 @@
 //                   taken while the count is 0, last offset, first
 //                   transactional batch) as wave scans.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
+#include "rpgpu_scan.h"
 
 namespace rpgpu {
 
@@ -128,12 +130,7 @@ __global__ __launch_bounds__(64) void fetch_summary_kernel(const uint8_t* __rest
         ok = ok && live;
         if (!ok) rc = 0;
         // exclusive running count in front of each batch (uint32 wrap)
-        uint32_t inc = rc;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const uint32_t t = __shfl_up(inc, s, 64);
-            if (lid >= (uint32_t)s) inc += t;
-        }
+        const uint32_t inc = wave_scan_incl(rc, lid);
         const uint32_t before = count + inc - rc;
         const uint64_t take = __ballot(ok && before == 0);  // base_offset = this batch's
         if (take) base = __shfl(bo, 63 - __builtin_clzll(take), 64);

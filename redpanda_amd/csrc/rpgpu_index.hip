@@ -10,6 +10,7 @@
 // validation result and the descriptor of each batch; writes at most one
 // 16-byte entry per batch, at the batch's own slot, so no plan is needed.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
 
 namespace rpgpu {
 

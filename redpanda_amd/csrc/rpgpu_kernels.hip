@@ -37,6 +37,8 @@
 // header CRC is not checked but computed after the Kafka CRC, over a header
 // that carries the computed crc (parser_utils.cc:122-128).
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
+#include "rpgpu_scan.h"
 #include "rpgpu_walk.h"
 
 namespace rpgpu {
@@ -627,53 +629,19 @@ __global__ __launch_bounds__(kScanBlock) void caps_kernel(const rpgpu_batch_desc
     const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
     uint32_t cap = 0;
     if (i < n) cap = index_cap(descs[i], data);
-    const uint32_t l = lane_id();
-    uint32_t x = cap;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        uint32_t t = __shfl_up(x, s, 64);
-        if (l >= (uint32_t)s) x += t;
-    }
-    const uint32_t wv = threadIdx.x >> 6;
-    if (l == 63) wsum[wv] = x;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (uint32_t k = 0; k < wv; k++) wbase += wsum[k];
+    const uint32_t first = block_scan_excl(cap, wsum, block_sum);
     if (i < n) {
         caps[i] = cap;
-        local_first[i] = wbase + x - cap;
-    }
-    if (threadIdx.x == kScanBlock - 1) {
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < kScanBlock / 64; k++) tot += wsum[k];
-        block_sum[blockIdx.x] = tot;
+        local_first[i] = first;
     }
 }
 
 // exclusive scan of block sums (single workgroup), total into *total_out
-__global__ __launch_bounds__(1024) void block_scan_kernel(uint64_t* __restrict__ block_sum, uint32_t nb,
-                                                          uint64_t* __restrict__ total_out) {
-    __shared__ uint64_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nb + 1023) / 1024;
-    const uint32_t lo = t * per, hi = (lo + per < nb) ? lo + per : nb;
-    uint64_t s = 0;
-    for (uint32_t k = lo; k < hi; k++) s += block_sum[k];
-    part[t] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {
-        uint64_t v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - s;  // exclusive
-    for (uint32_t k = lo; k < hi; k++) {
-        const uint64_t v = block_sum[k];
-        block_sum[k] = run;
-        run += v;
-    }
-    if (t == 1023 && total_out) *total_out = part[1023];
+__global__ __launch_bounds__(kScanBlock) void block_scan_kernel(uint64_t* block_sum, uint32_t nb,
+                                                                uint64_t* __restrict__ total_out) {
+    __shared__ uint64_t part[kScanBlock];
+    const uint64_t total = array_scan_excl(block_sum, block_sum, nb, part);
+    if (threadIdx.x == kScanBlock - 1 && total_out) *total_out = total;
 }
 
 // ---------------------------------------------- generic CRC32C over ranges
@@ -1111,12 +1079,13 @@ hipError_t launch_plan(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_
     uint64_t* block_sum;
     scratch_parts(d_scratch, n, &caps, &local_first, &block_sum);
     caps_kernel<<<nb, kScanBlock, 0, s>>>(d_descs, n, d_data, caps, local_first, block_sum);
-    block_scan_kernel<<<1, 1024, 0, s>>>(block_sum, nb, d_index_used);
-    return hipGetLastError();
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_block_scan(block_sum, nb, d_index_used, s);
 }
 
 hipError_t launch_block_scan(uint64_t* block_sum, uint32_t nb, uint64_t* total, hipStream_t s) {
-    block_scan_kernel<<<1, 1024, 0, s>>>(block_sum, nb, total);
+    block_scan_kernel<<<1, kScanBlock, 0, s>>>(block_sum, nb, total);
     return hipGetLastError();
 }
 

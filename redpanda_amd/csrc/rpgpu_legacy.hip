@@ -26,19 +26,14 @@
 //   legacy_copy_wave_kernel the listed keys and values, a wave each, 16 bytes
 //                         per lane.
 //   then the RECRC validation of the rewritten batches (launch_plan /
-//   launch_run) and legacy_patch_kernel, which stores both CRCs.
+//   launch_run) and recrc_patch_kernel, which stores both CRCs
+//   (launch_revalidate, rpgpu_rewrite.h).
 #include "rpgpu_device.h"
+#include "rpgpu_rewrite.h"
+#include "rpgpu_scan.h"
 #include "rpgpu_legacy.h"
 
 namespace rpgpu {
-
-hipError_t launch_plan(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                       uint64_t* d_index_used, void* d_scratch, hipStream_t s);
-hipError_t launch_run(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                      rpgpu_batch_result* d_res, rpgpu_record_index* d_index, uint64_t index_cap,
-                      const void* d_scratch, const uint32_t* d_tables, int grid, hipStream_t s,
-                      const Overlap* ov);
-size_t validate_scratch_bytes(uint32_t n);
 
 namespace {
 
@@ -127,39 +122,12 @@ __global__ __launch_bounds__(256) void legacy_scan_kernel(const rpgpu_batch_desc
     p.recs[i] = cand ? s.nmsg : 0;
 }
 
-// exclusive scan of in[0, n) into out (may be null) by one workgroup of 1024
-__device__ uint64_t block_excl_scan(const uint64_t* in, uint64_t* out, uint32_t n, uint64_t* part) {
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (n + 1023) / 1024;
-    const uint32_t lo = t * per < n ? t * per : n, hi = (lo + per < n) ? lo + per : n;
-    uint64_t s = 0;
-    for (uint32_t k = lo; k < hi; k++) s += in[k];
-    part[t] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024; off <<= 1) {
-        const uint64_t v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint64_t run = part[t] - s;
-    if (out)
-        for (uint32_t k = lo; k < hi; k++) {
-            const uint64_t v = in[k];
-            out[k] = run;
-            run += v;
-        }
-    const uint64_t total = part[1023];
-    __syncthreads();
-    return total;
-}
-
-__global__ __launch_bounds__(1024) void legacy_offsets_kernel(Parts p, uint32_t n, uint64_t* out_bytes,
-                                                              uint64_t* records_total) {
-    __shared__ uint64_t part[1024];
-    const uint64_t slots = block_excl_scan(p.slot_sz, p.slot_off, n, part);
-    const uint64_t msgs = block_excl_scan(p.msg_cnt, p.msg_first, n, part);
-    const uint64_t recs = block_excl_scan(p.recs, nullptr, n, part);
+__global__ __launch_bounds__(kScanBlock) void legacy_offsets_kernel(Parts p, uint32_t n, uint64_t* out_bytes,
+                                                                    uint64_t* records_total) {
+    __shared__ uint64_t part[kScanBlock];
+    const uint64_t slots = array_scan_excl(p.slot_sz, p.slot_off, n, part);
+    const uint64_t msgs = array_scan_excl(p.msg_cnt, p.msg_first, n, part);
+    const uint64_t recs = array_scan_excl<uint64_t>(p.recs, nullptr, n, part);
     if (threadIdx.x == 0) {
         p.totals[0] = slots;
         p.totals[1] = msgs;
@@ -411,17 +379,6 @@ __global__ __launch_bounds__(256) void legacy_copy_wave_kernel(const rpgpu_batch
     }
 }
 
-// stores the CRCs the validation of the rewritten batches computed
-__global__ __launch_bounds__(256) void legacy_patch_kernel(const rpgpu_legacy_result* __restrict__ lres,
-                                                           const rpgpu_batch_result* __restrict__ vres2, uint32_t n,
-                                                           uint8_t* __restrict__ out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || lres[i].verdict != RPGPU_V_OK) return;
-    uint8_t* o = out + lres[i].out_offset;
-    rplegacy::put_le(o, vres2[i].header_crc, 4);
-    rplegacy::put_le(o + 17, vres2[i].crc, 4);
-}
-
 }  // namespace
 
 size_t legacy_scratch_bytes(uint32_t n) { return vscratch_offset(n) + validate_scratch_bytes(n); }
@@ -437,7 +394,7 @@ hipError_t launch_legacy_plan(const rpgpu_batch_desc* d_sets, uint32_t n, const 
     legacy_scan_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_sets, n, d_data, p, nullptr, 0, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    legacy_offsets_kernel<<<1, 1024, 0, s>>>(p, n, d_out_bytes, d_records_total);
+    legacy_offsets_kernel<<<1, kScanBlock, 0, s>>>(p, n, d_out_bytes, d_records_total);
     return hipGetLastError();
 }
 
@@ -463,12 +420,8 @@ hipError_t launch_legacy_run(const rpgpu_batch_desc* d_sets, uint32_t n, const u
     if ((e = hipGetLastError()) != hipSuccess) return e;
     legacy_copy_wave_kernel<<<grid, 256, 0, s>>>(d_sets, d_data, p, d_lres, d_out, out_cap);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = launch_plan(d_out_descs, n, d_out, d_index_used, p.vscratch, s)) != hipSuccess) return e;
-    if ((e = launch_run(d_out_descs, n, d_out, d_vres2, d_index, index_cap, p.vscratch, d_tables, grid, s, nullptr)) !=
-        hipSuccess)
-        return e;
-    legacy_patch_kernel<<<nblk, 256, 0, s>>>(d_lres, d_vres2, n, d_out);
-    return hipGetLastError();
+    return launch_revalidate(d_out_descs, n, d_out, d_lres, d_vres2, d_index, index_cap, d_index_used, p.vscratch,
+                             d_tables, grid, s);
 }
 
 }  // namespace rpgpu

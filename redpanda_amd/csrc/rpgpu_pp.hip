@@ -38,11 +38,11 @@
 // (the index twice: plan and run), 4/3 of the field bytes and the skeleton
 // are written.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
+#include "rpgpu_scan.h"
 #include "rpgpu_pp.h"
 
 namespace rpgpu {
-
-hipError_t launch_block_scan(uint64_t* block_sum, uint32_t nb, uint64_t* total, hipStream_t s);
 
 namespace {
 
@@ -87,15 +87,6 @@ __device__ __forceinline__ uint32_t wave_index() { return (blockIdx.x * blockDim
 __device__ __forceinline__ uint32_t wave_count() { return (gridDim.x * blockDim.x) >> 6; }
 __device__ __forceinline__ unsigned long long* ull(uint64_t* p) { return reinterpret_cast<unsigned long long*>(p); }
 
-// inclusive scan over the wave's lanes
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, uint32_t l) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint64_t t = __shfl_up(v, s, 64);
-        if (l >= (uint32_t)s) v += t;
-    }
-    return v;
-}
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s, 64);
@@ -170,7 +161,7 @@ __global__ __launch_bounds__(256) void pp_range_kernel(const rpgpu_pp_range* __r
                         atomicMin(ull(p.key + r), (unsigned long long)rppp::event_key(pos, (uint32_t)j + 1));
                     break;
                 }
-                const uint64_t inc = wave_incl_scan(sz, l);
+                const uint64_t inc = wave_scan_incl(sz, l);
                 if (live) {
                     p.b_off[b] = run + inc - sz;
                     p.b_range[b] = g;
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(256) void pp_response_kernel(const rpgpu_pp_range* 
             const uint32_t g = R.first_range + (uint32_t)pos;
             const uint64_t sz = live ? p.r_off[g] : 0;
             const uint32_t rc = live ? p.r_recs[g] : 0;
-            const uint64_t inc = wave_incl_scan(sz, l);
+            const uint64_t inc = wave_scan_incl(sz, l);
             if (live) p.r_off[g] = run + inc - sz;
             run += __shfl(inc, 63, 64);
             recs += (uint32_t)wave_sum(rc);
@@ -293,7 +284,7 @@ __global__ __launch_bounds__(256) void pp_emit_kernel(const uint8_t* __restrict_
             rpgpu_record_index e = {0, 0, 0, 0, 0, 0};
             if (live) e = ix[c + l];
             const uint64_t sz = live ? rppp::object_var(e) + each : 0;
-            const uint64_t inc = wave_incl_scan(sz, l);
+            const uint64_t inc = wave_scan_incl(sz, l);
             const uint64_t at = run + inc - sz;
             run += __shfl(inc, 63, 64);
             rppp::Fields f = {nullptr, nullptr};

@@ -12,20 +12,15 @@
 //   sets_count_kernel  one lane per record set walks the chain of batch
 //                      headers (a dependent chain, but short: a few reads per
 //                      set), counts its batches; block-local scan
+//                      (rpgpu_scan.h), then block_scan_kernel over the blocks
 //   sets_emit_kernel   the same walk again, writing one descriptor per batch
 //   validate_kernel + walk_kernel over the batch descriptors (launch_run)
 //   sets_reduce_kernel one lane per set: the first failing batch in order
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
+#include "rpgpu_scan.h"
 
 namespace rpgpu {
-
-hipError_t launch_block_scan(uint64_t* block_sum, uint32_t nb, uint64_t* total, hipStream_t s);
-hipError_t launch_plan(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                       uint64_t* d_index_used, void* d_scratch, hipStream_t s);
-hipError_t launch_run(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,
-                      rpgpu_batch_result* d_res, rpgpu_record_index* d_index, uint64_t index_cap,
-                      const void* d_scratch, const uint32_t* d_tables, int grid, hipStream_t s,
-                      const Overlap* ov);
 
 namespace {
 // scratch: count[n] u32 | local[n] u32 | block_sum[nb] u64 | short[n] u8
@@ -94,26 +89,10 @@ __global__ __launch_bounds__(kScanBlock) void sets_count_kernel(const rpgpu_batc
         c = walk_set(sets[i], data, &sh, [](uint32_t, uint64_t, uint32_t) {});
         short_hdr[i] = sh ? 1 : 0;
     }
-    const uint32_t l = lane_id();
-    uint32_t x = c;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t t = __shfl_up(x, s, 64);
-        if (l >= (uint32_t)s) x += t;
-    }
-    const uint32_t wv = threadIdx.x >> 6;
-    if (l == 63) wsum[wv] = x;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (uint32_t k = 0; k < wv; k++) wbase += wsum[k];
+    const uint32_t first = block_scan_excl(c, wsum, block_sum);
     if (i < n) {
         count[i] = c;
-        local[i] = wbase + x - c;
-    }
-    if (threadIdx.x == kScanBlock - 1) {
-        uint64_t tot = 0;
-        for (uint32_t k = 0; k < kScanBlock / 64; k++) tot += wsum[k];
-        block_sum[blockIdx.x] = tot;
+        local[i] = first;
     }
 }
 
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(256) void sets_emit_kernel(const rpgpu_batch_desc* 
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const rpgpu_batch_desc set = sets[i];
-    const uint64_t first = block_base[i / kScanBlock] + local[i];
+    const uint64_t first = slot_offset(block_base, local, i);
     bool sh;
     walk_set(set, data, &sh, [&](uint32_t k, uint64_t off, uint32_t length) {
         if (first + k < cap) {
@@ -152,7 +131,7 @@ __global__ __launch_bounds__(256) void sets_reduce_kernel(uint32_t n, const uint
                                                           uint64_t cap, rpgpu_record_set_result* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint64_t first = block_base[i / kScanBlock] + local[i];
+    const uint64_t first = slot_offset(block_base, local, i);
     const uint32_t c = count[i];
     rpgpu_record_set_result r;
     r.verdict = RPGPU_V_OK;

@@ -27,6 +27,7 @@
 // appends; the result row takes the new attrs / max_timestamp / crc /
 // crc_expected / header_crc.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
 
 namespace rpgpu {
 namespace {

@@ -13,6 +13,7 @@
 // 64-bit atomics into the partition's row; a wave whose lanes all hit one
 // partition reduces in registers first and issues one atomic per column.
 #include "rpgpu_device.h"
+#include "rpgpu_launch.h"
 
 namespace rpgpu {
 

@@ -32,16 +32,14 @@
 #define RPGPU_WAVE_H
 
 #include "rpgpu_device.h"
+#include "rpgpu_scan.h"
 #include "rpgpu_zstd.h"
 
 namespace rpwave {
 
 using rpcodec::B16;
+using rpgpu::wave_scan_incl;
 
-__device__ __forceinline__ uint64_t shfl_up64(uint64_t x, int s) {
-    const uint32_t lo = __shfl_up((uint32_t)x, s, 64), hi = __shfl_up((uint32_t)(x >> 32), s, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t x, int s) {
     const uint32_t lo = __shfl_xor((uint32_t)x, s, 64), hi = __shfl_xor((uint32_t)(x >> 32), s, 64);
     return ((uint64_t)hi << 32) | lo;
@@ -50,14 +48,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t x, uint32_t l) {
     const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)x, (int)l);
     const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), (int)l);
     return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_scan_incl(uint64_t x, uint32_t lid) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint64_t y = shfl_up64(x, s);
-        if (lid >= (uint32_t)s) x += y;
-    }
-    return x;
 }
 __device__ __forceinline__ uint64_t wave_min64(uint64_t x) {
 #pragma unroll
