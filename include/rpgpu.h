@@ -1295,6 +1295,180 @@ int32_t rpgpu_append_run_device(rpgpu_ctx* ctx, const uint8_t* d_data, const rpg
                                 rpgpu_append_segment* d_segments, uint32_t seg_cap, void* d_scratch,
                                 void* hip_stream);
 
+/* ---- tiered-storage offset index: build and seek ------------------------------
+ * cloud_storage::offset_index (cloud_storage/remote_segment_index.{h,cc}): the
+ * sampled (Redpanda offset, Kafka offset, file position) index that every
+ * uploaded or hydrated segment gets (archival/ntp_archiver_service.cc:1139-1174,
+ * cloud_storage/remote_segment.cc:281-300) and that every remote read seeks
+ * with (find_kaf_offset, remote_segment.cc:257-275).  rpgpu_rsindex_plan_device
+ * + rpgpu_rsindex_run_device are remote_segment_index_builder riding the
+ * parser over a segment and offset_index::to_iobuf; rpgpu_rsindex_find_device
+ * is from_iobuf + find_rp_offset / find_kaf_offset.  Integer-only: the blobs
+ * are the reference's, byte for byte.
+ *
+ * Builder (remote_segment_index.cc:307-349), one segment = one stream of
+ * RPGPU_FMT_RP_DISK descriptors in file order (on-disk header: size_bytes i32
+ * at 4, base_offset i64 at 8, type i8 at 16, last_offset_delta i32 at 23):
+ *   delta = initial_delta; window = 0; pos = 0
+ *   for each batch:
+ *       if type == 2 (raft_configuration) or type == 19 (archival_metadata):
+ *           delta += last_offset_delta + 1
+ *       else if window >= sampling_step:
+ *           add(base_offset, base_offset - delta, pos); window = 0
+ *       window += size_bytes; pos += size_bytes   (the parser's running sum,
+ *                                                  storage/parser.cc:132-138)
+ * Every other type is sampled like data (ghost batches and unknown types too);
+ * a configuration batch that arrives when the window is full defers the sample
+ * to the next other batch; sampling_step 0 samples the first such batch, 1
+ * does not.  Only the 61-byte headers are read, no CRC is checked: the parser
+ * that delivered the descriptors did that.
+ *
+ * offset_index::add (:37-63) fills three 16-entry write buffers cyclically and,
+ * when the position wraps to 0 mod 16, appends them as one row to each of
+ * three delta-FOR encoders (utils/delta_for.h).  The buffers are never
+ * cleared: slots at and past (samples mod 16) keep the previous row's values
+ * (zero before the first flush), and to_iobuf serializes all 16.
+ *
+ * Delta-FOR row (delta_for.h:276-284, 515-764): the rp and Kafka streams use
+ * delta_xor (buf[i] = row[i] ^ prev), the file stream delta_delta
+ * (buf[i] = row[i] - prev - file_pos_step); prev starts at the encoder's
+ * initial value (base rp, base Kafka, 0) and carries across rows.  nbits =
+ * bit_width(OR of buf); the row is one byte nbits, a 32-bit section if nbits
+ * >= 32, a 16-bit section if what is left >= 16, an 8-bit section if what is
+ * left >= 8 (each: the 16 values' next low bits, little-endian, value-major),
+ * then the remaining r = 1..7 bits as 16 r-bit fields in one little-endian bit
+ * string of 2r bytes, value i at bit i * r; nbits == 64 is 16 little-endian
+ * uint64.  A row takes 1 + 2 * nbits bytes.  delta_delta::encode asserts
+ * row[i] - prev >= file_pos_step when a row is flushed: such a segment gets
+ * RPGPU_RSINDEX_DELTA_ASSERT (possible only with sampling_step <
+ * file_pos_step); the same delta in the unflushed tail goes unnoticed, as in
+ * the reference.
+ *
+ * Blob (to_iobuf :216-258 in a serde envelope, serde/serde.h:515-565; all
+ * little-endian, nothing aligned):
+ *     0, 1  version 1, compat version 1
+ *     2     u32 payload size = blob size - 6
+ *     6     min_file_pos_step i64        14  num_elements u64 (samples)
+ *    22, 30 base_rp, last_rp             38, 46  base_kaf, last_kaf
+ *    54, 62 base_file (0), last_file
+ *    70     u32 16 + 16 x i64 rp write buffer; 202 the Kafka one; 334 the file one
+ *   466     u32 length + rp stream, u32 length + Kafka stream, u32 length + file stream
+ * last_* is the encoder's _last: the last value of the last flushed row, or the
+ * initial value without rows.  Blob size = 478 + the three stream lengths.
+ *
+ * Plan (rpgpu_rsindex_scratch_bytes(n, nsegs) bytes of scratch, shared with the
+ * run): reads d_segs, d_descs and the headers at desc.offset.  The segments'
+ * descriptor ranges must not overlap.  It fills every field of every result
+ * row; d_totals[0] is the smallest out_cap that holds every OK blob,
+ * d_totals[1] the samples of the OK segments.  RPGPU_RSINDEX_BAD_BATCH: a
+ * descriptor index >= n, a descriptor that is not RPGPU_FMT_RP_DISK or shorter
+ * than 61 bytes, or a header whose size_bytes < 61; bad_batch is the index of
+ * the first one in d_descs and samples, rows, config_batches, final_delta and
+ * stream_bytes describe the batches in front of it (a segment that would also
+ * assert is BAD_BATCH).  A BAD_BATCH or
+ * DELTA_ASSERT segment has out_bytes 0 and the three stream sizes 0, and gets
+ * no blob.  Blobs lie at out_offset, an exclusive scan of the OK segments'
+ * out_bytes with every start on a 16-byte boundary.
+ * Run: reads the plan's scratch and d_segs (the same rows), not d_data, and
+ * writes each blob whole or not at all: one that ends past out_cap gets
+ * RPGPU_RSINDEX_NO_ROOM, every other field is kept.  It writes nothing outside
+ * the OK blobs and nothing at or past out_cap.  A plan may be run any number
+ * of times; every run sets every status again.
+ *
+ * Find, one query per row: d_blobs + blob_offset is any blob to_iobuf could
+ * have written.  RPGPU_RSINDEX_BAD_BLOB: blob_bytes < 478, version or compat
+ * version not 1, size field + 6 != blob_bytes, a write-buffer count != 16,
+ * stream lengths that do not end at blob_bytes, or, in any of the three
+ * streams, a chain of num_elements / 16 rows with an nbits above 64 or a row
+ * that ends past its stream.  Nothing outside [blob_offset, blob_offset +
+ * blob_bytes) is read.  Lookup (maybe_find_offset :65-103, _find_under
+ * :289-305) on the rp (by_rp != 0) or Kafka column:
+ *   1. decode the searched stream; the candidate is the last element <
+ *      upper_bound, stopping at the first element >= upper_bound;
+ *   2. without a candidate, or if it is element 16 * rows - 1: scan write-buffer
+ *      slots [0, num_elements & 15) of the searched column the same way; a hit
+ *      answers with the three write-buffer values of that slot
+ *      (from_write_buffer = 1, ix = the slot); no hit and no candidate is
+ *      RPGPU_RSINDEX_NONE (every other field 0);
+ *   3. otherwise the answer is the candidate's value and element ix of the
+ *      other two decoded streams (the file stream decodes with the blob's
+ *      min_file_pos_step and base_file).
+ * The answer seeds rpgpu_remote_read (remote_segment.cc:237-254): offset +=
+ * file_pos, cur_rp_offset = rp_offset, cur_delta = rp_offset - kaf_offset.
+ *
+ * Hand vector: 60 headers, batch k has type 2 and last_offset_delta 2 if k ==
+ * 7, else type 1 and last_offset_delta 0; size_bytes = 100 + k % 3; base
+ * offsets consecutive from 1000 (the configuration batch takes three).  Base rp
+ * 1000, base Kafka 990, initial delta 10, both steps 150.  29 samples, one row
+ * per stream, blob 527 bytes (payload size 09020000); last_rp 1034, last_kaf
+ * 1021, last_file 3231; streams
+ *   rp    0b0206021c06020e020602fe0206020e02000000c00100
+ *   Kafka 06be6004822318822718822318
+ *   file  06335dcf743dd3f54cd7335dcf
+ * first samples (1002, 992, 201), (1004, 994, 403), (1006, 996, 606), (1010,
+ * 997, 807); rp write-buffer slots 13..15 are the stale 1030, 1032, 1034.
+ * find_kaf(1003) -> element 5 (1014, 1001, 1212); find_kaf(1022) -> element 15
+ * (1034, 1021, 3231); find_kaf(1030) -> write-buffer slot 3 (1042, 1029, 4039);
+ * find_kaf(992) -> none; find_rp(1036) -> element 15 (slot 0 holds 1036, not
+ * below the bound); find_rp(99999) -> slot 12 (1060, 1047, 5857). */
+typedef struct rpgpu_rsindex_segment { /* one stream = one offset_index */
+    uint32_t first_batch, batch_count; /* its descriptors, in file order                   */
+    int64_t base_rp_offset;            /* offset_index initial_rp                          */
+    int64_t base_kafka_offset;         /* offset_index initial_kaf                         */
+    int64_t initial_delta;             /* remote_segment_index_builder initial_delta       */
+    int64_t file_pos_step;             /* offset_index file_pos_step (64 KiB at call sites) */
+    uint64_t sampling_step;            /* builder's sampling_step (64 KiB at call sites)   */
+} rpgpu_rsindex_segment;               /* 48 bytes */
+
+enum rpgpu_rsindex_status {
+    RPGPU_RSINDEX_OK = 0,
+    RPGPU_RSINDEX_NO_ROOM = 1,
+    RPGPU_RSINDEX_BAD_BATCH = 2,
+    RPGPU_RSINDEX_DELTA_ASSERT = 3
+};
+typedef struct rpgpu_rsindex_result {
+    int32_t status;          /* enum rpgpu_rsindex_status                     */
+    uint32_t samples;        /* offset_index _pos (num_elements)              */
+    uint32_t rows;           /* rows flushed to each encoder: samples / 16    */
+    uint32_t config_batches; /* type 2 and type 19 batches                    */
+    uint32_t bad_batch;      /* BAD_BATCH: the first offending descriptor     */
+    uint32_t rp_bytes, kaf_bytes, file_bytes; /* the three streams            */
+    uint32_t out_bytes;      /* 478 + the three; 0 without a blob             */
+    uint32_t reserved;
+    int64_t final_delta;     /* _running_delta after the stream               */
+    uint64_t stream_bytes;   /* sum of size_bytes: the parser's position      */
+    uint64_t out_offset;     /* the blob in d_out, 16-byte aligned            */
+} rpgpu_rsindex_result;      /* 64 bytes */
+
+size_t rpgpu_rsindex_scratch_bytes(uint32_t n, uint32_t nsegs);
+int32_t rpgpu_rsindex_plan_device(rpgpu_ctx* ctx, const uint8_t* d_data, const rpgpu_batch_desc* d_descs, uint32_t n,
+                                  const rpgpu_rsindex_segment* d_segs, uint32_t nsegs,
+                                  rpgpu_rsindex_result* d_results, uint64_t* d_totals, void* d_scratch,
+                                  void* hip_stream);
+int32_t rpgpu_rsindex_run_device(rpgpu_ctx* ctx, const rpgpu_rsindex_segment* d_segs, uint32_t nsegs,
+                                 rpgpu_rsindex_result* d_results, uint8_t* d_out, uint64_t out_cap, void* d_scratch,
+                                 void* hip_stream);
+
+typedef struct rpgpu_rsindex_query {
+    uint64_t blob_offset;    /* the blob in d_blobs                           */
+    uint32_t blob_bytes;
+    uint32_t by_rp;          /* != 0: find_rp_offset, else find_kaf_offset    */
+    int64_t upper_bound;
+    uint64_t reserved;
+} rpgpu_rsindex_query;       /* 32 bytes */
+
+enum rpgpu_rsindex_find_status { RPGPU_RSINDEX_FOUND = 0, RPGPU_RSINDEX_NONE = 1, RPGPU_RSINDEX_BAD_BLOB = 2 };
+typedef struct rpgpu_rsindex_found { /* offset_index::find_result */
+    int32_t status;          /* enum rpgpu_rsindex_find_status                */
+    uint32_t from_write_buffer;
+    uint64_t ix;             /* element of the decoded streams, or the slot   */
+    int64_t rp_offset, kaf_offset, file_pos;
+    uint64_t reserved;
+} rpgpu_rsindex_found;       /* 48 bytes */
+
+int32_t rpgpu_rsindex_find_device(rpgpu_ctx* ctx, const uint8_t* d_blobs, const rpgpu_rsindex_query* d_queries,
+                                  uint32_t nq, rpgpu_rsindex_found* d_found, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,22 @@ APPEND_SEGMENT_DTYPE = np.dtype([("log", "<u4"), ("flags", "<u4"), ("first", "<u
                                  ("base_offset", "<i8"), ("file_pos", "<u8"), ("out_offset", "<u8"), ("bytes", "<u8")])
 assert APPEND_LOG_DTYPE.itemsize == 32 and APPEND_BATCH_DTYPE.itemsize == 32
 assert APPEND_LOG_RESULT_DTYPE.itemsize == 64 and APPEND_SEGMENT_DTYPE.itemsize == 48
+# tiered-storage offset index (rpgpu_rsindex_*)
+RSINDEX_OK, RSINDEX_NO_ROOM, RSINDEX_BAD_BATCH, RSINDEX_DELTA_ASSERT = range(4)  # rpgpu_rsindex_result.status
+RSINDEX_FOUND, RSINDEX_NONE, RSINDEX_BAD_BLOB = range(3)  # rpgpu_rsindex_found.status
+RSINDEX_SEGMENT_DTYPE = np.dtype([("first_batch", "<u4"), ("batch_count", "<u4"), ("base_rp_offset", "<i8"),
+                                  ("base_kafka_offset", "<i8"), ("initial_delta", "<i8"), ("file_pos_step", "<i8"),
+                                  ("sampling_step", "<u8")])
+RSINDEX_RESULT_DTYPE = np.dtype([("status", "<i4"), ("samples", "<u4"), ("rows", "<u4"), ("config_batches", "<u4"),
+                                 ("bad_batch", "<u4"), ("rp_bytes", "<u4"), ("kaf_bytes", "<u4"),
+                                 ("file_bytes", "<u4"), ("out_bytes", "<u4"), ("reserved", "<u4"),
+                                 ("final_delta", "<i8"), ("stream_bytes", "<u8"), ("out_offset", "<u8")])
+RSINDEX_QUERY_DTYPE = np.dtype([("blob_offset", "<u8"), ("blob_bytes", "<u4"), ("by_rp", "<u4"),
+                                ("upper_bound", "<i8"), ("reserved", "<u8")])
+RSINDEX_FOUND_DTYPE = np.dtype([("status", "<i4"), ("from_write_buffer", "<u4"), ("ix", "<u8"), ("rp_offset", "<i8"),
+                                ("kaf_offset", "<i8"), ("file_pos", "<i8"), ("reserved", "<u8")])
+assert RSINDEX_SEGMENT_DTYPE.itemsize == 48 and RSINDEX_RESULT_DTYPE.itemsize == 64
+assert RSINDEX_QUERY_DTYPE.itemsize == 32 and RSINDEX_FOUND_DTYPE.itemsize == 48
 INDEX_ENTRY_DTYPE = np.dtype([("relative_offset", "<u4"), ("relative_time", "<u4"), ("position", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 32 and SEGMENT_STATE_DTYPE.itemsize == 48 and INDEX_ENTRY_DTYPE.itemsize == 16
 assert INDEX_DTYPE.itemsize == 32 and RP_HEADER_DTYPE.itemsize == 61
@@ -331,6 +347,10 @@ def lib() -> C.CDLL:
         _sig(L.rpgpu_append_plan_device, _i32, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp)
         _sig(L.rpgpu_append_run_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u64,
              _vp, _vp, _u32, _vp, _u32, _vp, _vp)
+        _sig(L.rpgpu_rsindex_scratch_bytes, C.c_size_t, _u32, _u32)
+        _sig(L.rpgpu_rsindex_plan_device, _i32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_rsindex_run_device, _i32, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp)
+        _sig(L.rpgpu_rsindex_find_device, _i32, _vp, _vp, _vp, _u32, _vp, _vp)
         _LIB = L
     return _LIB
 
@@ -370,4 +390,6 @@ EXPORTED = [
     "rpgpu_legacy_run_device", "rpgpu_convert_message_set", "rpgpu_legacy_kafka_error_code",
     "rpgpu_pp_fetch_scratch_bytes", "rpgpu_pp_fetch_plan_device", "rpgpu_pp_fetch_run_device",
     "rpgpu_append_scratch_bytes", "rpgpu_append_plan_device", "rpgpu_append_run_device",
+    "rpgpu_rsindex_scratch_bytes", "rpgpu_rsindex_plan_device", "rpgpu_rsindex_run_device",
+    "rpgpu_rsindex_find_device",
 ]

@@ -457,6 +457,39 @@ int32_t rpgpu_append_run_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu
     return RPGPU_OK;
 }
 
+size_t rpgpu_rsindex_scratch_bytes(uint32_t n, uint32_t nsegs) { return rpgpu::rsindex_scratch_bytes(n, nsegs); }
+
+int32_t rpgpu_rsindex_plan_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs, uint32_t n,
+                                  const rpgpu_rsindex_segment* d_segs, uint32_t nsegs,
+                                  rpgpu_rsindex_result* d_results, uint64_t* d_totals, void* d_scratch,
+                                  void* hip_stream) {
+    if (!c || !d_totals || (n && (!d_data || !d_descs)) || (nsegs && (!d_segs || !d_results || !d_scratch)))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_rsindex_plan(d_data, d_descs, n, d_segs, nsegs, d_results, d_totals, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "offset index plan launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_rsindex_run_device(rpgpu_ctx* c, const rpgpu_rsindex_segment* d_segs, uint32_t nsegs,
+                                 rpgpu_rsindex_result* d_results, uint8_t* d_out, uint64_t out_cap, void* d_scratch,
+                                 void* hip_stream) {
+    if (!c || (nsegs && (!d_segs || !d_results || !d_scratch)) || (out_cap && !d_out)) return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_rsindex_run(d_segs, nsegs, d_results, d_out, out_cap, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "offset index run launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_rsindex_find_device(rpgpu_ctx* c, const uint8_t* d_blobs, const rpgpu_rsindex_query* d_queries,
+                                  uint32_t nq, rpgpu_rsindex_found* d_found, void* hip_stream) {
+    if (!c || (nq && (!d_blobs || !d_queries || !d_found))) return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_rsindex_find(d_blobs, d_queries, nq, d_found, s);
+    if (e != hipSuccess) return fail(c, e, "offset index find launch");
+    return RPGPU_OK;
+}
+
 int32_t rpgpu_batch_timequery_device(rpgpu_ctx* c, const rpgpu_batch_result* d_results, uint32_t n,
                                      const rpgpu_record_index* d_index, const rpgpu_timequery* d_queries,
                                      uint32_t nq, rpgpu_timequery_result* d_out, void* hip_stream) {

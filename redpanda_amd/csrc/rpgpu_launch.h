@@ -147,5 +147,15 @@ hipError_t launch_append_run(const uint8_t* d_data, const rpgpu_batch_desc* d_de
                              rpgpu_append_segment* d_segments, uint32_t seg_cap, void* d_scratch,
                              const uint32_t* d_tables, hipStream_t s);
 
+// ---- rpgpu_rsindex.hip
+size_t rsindex_scratch_bytes(uint32_t n, uint32_t nsegs);
+hipError_t launch_rsindex_plan(const uint8_t* d_data, const rpgpu_batch_desc* d_descs, uint32_t n,
+                               const rpgpu_rsindex_segment* d_segs, uint32_t nsegs, rpgpu_rsindex_result* d_results,
+                               uint64_t* d_totals, void* d_scratch, hipStream_t s);
+hipError_t launch_rsindex_run(const rpgpu_rsindex_segment* d_segs, uint32_t nsegs, rpgpu_rsindex_result* d_results,
+                              uint8_t* d_out, uint64_t out_cap, void* d_scratch, hipStream_t s);
+hipError_t launch_rsindex_find(const uint8_t* d_blobs, const rpgpu_rsindex_query* d_queries, uint32_t nq,
+                               rpgpu_rsindex_found* d_found, hipStream_t s);
+
 }  // namespace rpgpu
 #endif

@@ -733,6 +733,72 @@ class Engine:
                     out_results=d_ores.cpu().numpy().view(abi.RESULT_DTYPE)[:rows_cap + 1].copy(),
                     totals=totals, out_cap=out_cap, rows_cap=rows_cap, seg_cap=seg_cap)
 
+    def rsindex_build(self, data: np.ndarray, descs: np.ndarray, segs: np.ndarray, out_cap: int | None = None,
+                      plans: int = 1, runs: int = 1, fill: int | None = None, guard: int = 0) -> dict:
+        """rpgpu_rsindex_plan_device / rpgpu_rsindex_run_device: the tiered-storage
+        offset index of every segment (RSINDEX_SEGMENT_DTYPE rows over on-disk
+        descriptors) as the bytes of offset_index::to_iobuf.  Returns host
+        copies: plan_results (after the plan), results (after the run), totals
+        (the plan's two), out (out_cap bytes, the plan's total by default, then
+        `guard` more; pre-filled with `fill` when given, else zero) and out_cap."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        descs = np.ascontiguousarray(descs, dtype=abi.DESC_DTYPE)
+        segs = np.ascontiguousarray(segs, dtype=abi.RSINDEX_SEGMENT_DTYPE)
+        n, ns = len(descs), len(segs)
+
+        def up(a):
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(64, np.uint8)).to(dev)
+
+        d_data = up(np.concatenate([data, np.zeros(abi.ARENA_TAIL_PAD, np.uint8)]))
+        d_descs, d_segs = up(descs), up(segs)
+        d_res = torch.zeros(max(ns, 1) * abi.RSINDEX_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_tot = torch.zeros(2, dtype=torch.int64, device=dev)
+        d_scr = torch.zeros(max(int(self._lib.rpgpu_rsindex_scratch_bytes(n, ns)), 1), dtype=torch.uint8, device=dev)
+        for _ in range(plans):
+            rc = self._lib.rpgpu_rsindex_plan_device(self._ctx, d_data.data_ptr(), d_descs.data_ptr(), n,
+                                                     d_segs.data_ptr(), ns, d_res.data_ptr(), d_tot.data_ptr(),
+                                                     d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_rsindex_plan_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        totals = d_tot.cpu().numpy().astype(np.uint64)
+        plan_results = d_res.cpu().numpy().view(abi.RSINDEX_RESULT_DTYPE)[:ns].copy()
+        out_cap = int(totals[0]) if out_cap is None else out_cap
+        d_out = torch.full((max(out_cap + guard, 1),), 0 if fill is None else fill, dtype=torch.uint8, device=dev)
+        for _ in range(runs):
+            rc = self._lib.rpgpu_rsindex_run_device(self._ctx, d_segs.data_ptr(), ns, d_res.data_ptr(),
+                                                    d_out.data_ptr(), out_cap, d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_rsindex_run_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return dict(plan_results=plan_results, results=d_res.cpu().numpy().view(abi.RSINDEX_RESULT_DTYPE)[:ns].copy(),
+                    totals=totals, out=d_out.cpu().numpy()[: out_cap + guard].copy(), out_cap=out_cap)
+
+    def rsindex_find(self, blobs: np.ndarray, queries: np.ndarray) -> np.ndarray:
+        """rpgpu_rsindex_find_device: find_rp_offset / find_kaf_offset per query
+        (RSINDEX_QUERY_DTYPE rows naming serialized indexes in `blobs`).  The
+        device buffer holds exactly the bytes of `blobs`."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        blobs = np.ascontiguousarray(blobs, dtype=np.uint8)
+        queries = np.ascontiguousarray(queries, dtype=abi.RSINDEX_QUERY_DTYPE)
+        nq = len(queries)
+        d_blobs = torch.from_numpy(blobs.copy() if blobs.size else np.zeros(1, np.uint8)).to(dev)
+        d_q = torch.from_numpy(queries.view(np.uint8).reshape(-1).copy() if nq else np.zeros(32, np.uint8)).to(dev)
+        d_found = torch.full((max(nq, 1) * abi.RSINDEX_FOUND_DTYPE.itemsize,), 0xA5, dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_rsindex_find_device(self._ctx, d_blobs.data_ptr(), d_q.data_ptr(), nq,
+                                                 d_found.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_rsindex_find_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return d_found.cpu().numpy().view(abi.RSINDEX_FOUND_DTYPE)[:nq].copy()
+
     def batch_timequery(self, results: np.ndarray, index: np.ndarray, queries: np.ndarray) -> np.ndarray:
         """rpgpu_batch_timequery_device (storage::batch_timequery) per query."""
         import torch
