@@ -734,7 +734,9 @@ enum rpgpu_parse_mode {
 
 typedef struct rpgpu_segment_read {
     uint64_t offset;          /* the segment's bytes in the arena             */
-    uint64_t length;          /* bytes the input stream yields                */
+    uint64_t length;          /* bytes the input stream yields: any value, the
+                                 parser's positions are 64-bit (a batch's own
+                                 size_bytes is an int32)                      */
     uint32_t desc_first;      /* first output descriptor slot                 */
     uint32_t desc_cap;        /* slots available                              */
     uint32_t partition;       /* copied into the emitted descriptors          */
@@ -803,7 +805,8 @@ int32_t rpgpu_segment_parse_device(rpgpu_ctx* ctx, const uint8_t* d_data, const 
  * or RPGPU_V_REMOTE_DELTA_ASSERT. */
 typedef struct rpgpu_remote_read {
     uint64_t offset;          /* the stream's bytes in the arena              */
-    uint64_t length;          /* bytes the input stream yields                */
+    uint64_t length;          /* bytes the input stream yields: any value, as
+                                 rpgpu_segment_read.length                    */
     uint32_t desc_first, desc_cap;
     uint32_t gap_first, gap_cap;
     uint32_t partition;       /* copied into the emitted descriptors          */

@@ -706,7 +706,6 @@ __global__ __launch_bounds__(kValidateThreads) void segment_parse_kernel(
         uint32_t accepted = 0, skipped = 0;
         int64_t start_offset = rd.start_offset, expected = rd.expected_next_batch;
         uint64_t cfg_bytes = rd.bytes_consumed;
-        const __amdgpu_buffer_rsrc_t rs = batch_rsrc(seg);
         for (;;) {
             const uint64_t rem = len - pos;
             if (rem == 0) {
@@ -717,9 +716,11 @@ __global__ __launch_bounds__(kValidateThreads) void segment_parse_kernel(
                 err = RPGPU_V_STREAM_SHORT;
                 break;
             }
-            // the 64-byte header window at pos (segments are < 2 GiB apart
-            // from their base; the arena's tail pad covers the 3 bytes past 61)
-            const uint32_t hv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int32_t)(pos + 4 * (l & 15)), 0, 0);
+            // the 64-byte header window at pos: pos is wave-uniform and 64-bit,
+            // so the resource is rebuilt at seg + pos (a read may be any length;
+            // the arena's tail pad covers the 3 bytes past 61)
+            const __amdgpu_buffer_rsrc_t rs = batch_rsrc(seg + pos);
+            const uint32_t hv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int32_t)(4 * (l & 15)), 0, 0);
             Img64 H;
 #pragma unroll
             for (int i = 0; i < 16; i++) H.w[i] = rdl(hv, i);
@@ -871,7 +872,6 @@ __global__ __launch_bounds__(kValidateThreads) void remote_parse_kernel(
         uint32_t accepted = 0, skipped = 0, ngaps = 0;
         int64_t start_offset = rd.start_offset, delta = rd.cur_delta, cur_rp = rd.cur_rp_offset;
         uint64_t cfg_bytes = rd.bytes_consumed;
-        const __amdgpu_buffer_rsrc_t rs = batch_rsrc(seg);
         for (;;) {
             const uint64_t rem = len - pos;
             if (rem == 0) {
@@ -882,7 +882,8 @@ __global__ __launch_bounds__(kValidateThreads) void remote_parse_kernel(
                 err = RPGPU_V_STREAM_SHORT;
                 break;
             }
-            const uint32_t hv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int32_t)(pos + 4 * (l & 15)), 0, 0);
+            const __amdgpu_buffer_rsrc_t rs = batch_rsrc(seg + pos);  // as in segment_parse_kernel
+            const uint32_t hv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int32_t)(4 * (l & 15)), 0, 0);
             Img64 H;
 #pragma unroll
             for (int i = 0; i < 16; i++) H.w[i] = rdl(hv, i);

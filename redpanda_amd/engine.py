@@ -414,11 +414,18 @@ class Engine:
 
         dev = torch.device("cuda", self.device)
         data = np.ascontiguousarray(data, dtype=np.uint8)
+        return self.segment_parse_device(torch.from_numpy(data.copy()).to(dev), reads)
+
+    def segment_parse_device(self, d_data, reads: np.ndarray) -> dict:
+        """segment_parse over an arena that is already a device uint8 tensor
+        (with its 64-byte tail pad)."""
+        import torch
+
+        dev = d_data.device
         reads = np.ascontiguousarray(reads, dtype=abi.SEGMENT_READ_DTYPE)
         n = len(reads)
         ncap = int((reads["desc_first"].astype(np.int64) + reads["desc_cap"]).max()) if n else 0
         sh = torch.cuda.current_stream(dev).cuda_stream
-        d_data = torch.from_numpy(data.copy()).to(dev)
         d_reads = torch.from_numpy(reads.view(np.uint8).copy()).to(dev)
         d_res = torch.zeros(max(n, 1) * abi.SEGMENT_PARSE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         d_descs = torch.zeros(max(ncap, 1) * 24, dtype=torch.uint8, device=dev)
@@ -439,12 +446,19 @@ class Engine:
 
         dev = torch.device("cuda", self.device)
         data = np.ascontiguousarray(data, dtype=np.uint8)
+        return self.remote_segment_parse_device(torch.from_numpy(data.copy()).to(dev), reads)
+
+    def remote_segment_parse_device(self, d_data, reads: np.ndarray) -> dict:
+        """remote_segment_parse over an arena that is already a device uint8
+        tensor (with its 64-byte tail pad)."""
+        import torch
+
+        dev = d_data.device
         reads = np.ascontiguousarray(reads, dtype=abi.REMOTE_READ_DTYPE)
         n = len(reads)
         ncap = int((reads["desc_first"].astype(np.int64) + reads["desc_cap"]).max()) if n else 0
         gcap = int((reads["gap_first"].astype(np.int64) + reads["gap_cap"]).max()) if n else 0
         sh = torch.cuda.current_stream(dev).cuda_stream
-        d_data = torch.from_numpy(data.copy()).to(dev)
         d_reads = torch.from_numpy(reads.view(np.uint8).copy()).to(dev)
         d_res = torch.zeros(max(n, 1) * abi.REMOTE_PARSE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         d_descs = torch.zeros(max(ncap, 1) * 24, dtype=torch.uint8, device=dev)
