@@ -112,8 +112,17 @@ enum rpgpu_verdict {
     /* remote segment reader (cloud_storage/remote_segment.cc:808-815) */
     RPGPU_V_REMOTE_DELTA_ASSERT = 38, /* vassert in rp_to_kafka: a batch's Redpanda
                                       offset below the offset-translation delta */
+    /* 39, 41 and 42 appear only in rpgpu_segidx_tracked.status
+     * (rpgpu_segidx_track_device), never in an rpgpu_batch_result */
+    RPGPU_V_INDEX_NON_DATA_ASSERT = 39, /* vassert in maybe_index (index_state.cc:61): a
+                                     user-data batch while non_data_timestamps is set
+                                     and the index does not hold exactly one entry
+                                     (only from a hostile hydrated state)         */
     RPGPU_V_SKIPPED = 40,          /* not decompressed: no RPGPU_OP_DECOMP, not
                                       validated OK, or not compressed        */
+    RPGPU_V_INDEX_NO_ROOM = 41,    /* the next entry would pass the state's entry_cap */
+    RPGPU_V_INDEX_BAD_STATE = 42,  /* the state's slot or the segment's batches lie
+                                     outside the arrays                          */
     /* legacy MessageSets, produce versions below 3 (rpgpu_legacy_*; kafka/protocol/
      * kafka_batch_adapter.cc:215-301, kafka/protocol/legacy_message.h) */
     RPGPU_V_LEGACY_MAGIC = 50,           /* magic not 0 or 1: legacy_error            */
@@ -1200,8 +1209,8 @@ int32_t rpgpu_pp_fetch_run_device(rpgpu_ctx* ctx, const uint8_t* d_data, const r
  * written.  index_first / index_count are unchanged: they still name the
  * input index, whose offset column holds the produce-time offsets.  The
  * output feeds rpgpu_run_device, rpgpu_kafka_serialize_device and, for ROLLED
- * segments, rpgpu_segment_index_device without conversion (carrying index
- * state into a continuing segment is the caller's: DESIGN.md §7).
+ * segments, rpgpu_segment_index_device without conversion; a continuing
+ * segment's index goes on from its state with rpgpu_segidx_track_device.
  * A segment row (rpgpu_append_segment) is opened at each roll, and for the
  * continuing segment when the first eligible batch reaches it with left > 0.
  * A ghost batch's file_pos is the position the next written batch takes.
@@ -1471,6 +1480,255 @@ typedef struct rpgpu_rsindex_found { /* offset_index::find_result */
 
 int32_t rpgpu_rsindex_find_device(rpgpu_ctx* ctx, const uint8_t* d_blobs, const rpgpu_rsindex_query* d_queries,
                                   uint32_t nq, rpgpu_rsindex_found* d_found, void* hip_stream);
+
+/* ---- segment index life cycle: track, write, hydrate, seek ---------------------
+ * What the broker does with a segment's offset/time index after recovery built
+ * it, on index_state rows that stay on the device:
+ *   rpgpu_segidx_track_device       segment_index::maybe_track (storage/segment_index.cc:98-120)
+ *                                   + index_state::maybe_index (storage/index_state.cc:38-109)
+ *                                   continued from any state;
+ *   rpgpu_segidx_write_plan_device, segment_index::flush -> serde::to_iobuf(index_state)
+ *   rpgpu_segidx_write_run_device   (segment_index.cc:237-263, index_state.cc:124-147):
+ *                                   the bytes of the .base_index file;
+ *   rpgpu_segidx_hydrate_device     segment_index::materialize_index_from_file
+ *                                   (segment_index.cc:205-229, index_state.cc:149-219,
+ *                                   index_state_serde_compat.h:46-101);
+ *   rpgpu_segidx_find_device        find_nearest(offset) (segment_index.cc:140-163),
+ *                                   find_nearest(timestamp) (:122-138, index_state.h:166-190),
+ *                                   find_highest_timestamp_before (:306-323).
+ * Integer-only: blobs, states and answers are the reference's, byte for byte.
+ *
+ * State i is one index_state plus the two segment_index members tracking needs.
+ * Its entries are rows [entry_first, entry_first + entries) of one shared
+ * rpgpu_index_entry array of nentries rows; entry_cap is the size of its slot.
+ * Every entry point checks entry_first + entry_cap <= nentries and entries <=
+ * entry_cap before it touches the array (a row that fails is *_BAD_STATE).
+ *
+ * Track: segment row s (first_batch, batch_count, file_base, step,
+ * internal_topic; its base_offset and with_offset are ignored, the state's
+ * hold) continues state s.  The recurrence is rpgpu_segment_index_device's,
+ * started from the state: a fresh state is base_offset, with_offset, monotonic
+ * = 1, last_batch_max_timestamp = -1 (model::timestamp{}), everything else 0.
+ * position = desc.offset - file_base in wrapping 64-bit arithmetic; when the
+ * first user-data batch follows a configuration batch that was indexed first,
+ * entry 0's relative_time is rewritten with the batch's absolute, clamped
+ * max_timestamp (index_state.cc:62-63).  Tracking stops in front of the first
+ * batch whose verdict is not OK (status OK), whose base offset lies below the
+ * state's (RPGPU_V_INDEX_OFFSET_BELOW_BASE), that is user data while
+ * non_data_timestamps is set and entries != 1 (RPGPU_V_INDEX_NON_DATA_ASSERT),
+ * or whose entry would not fit entry_cap (RPGPU_V_INDEX_NO_ROOM); the state
+ * then is the state in front of that batch, `tracked` says how many batches
+ * went in, and tracking can go on from there.  Nothing is written past the cap.
+ *
+ * Blob (current format; all little-endian, nothing aligned), n = entries:
+ *     0  u8 5, u8 4        version, compat version
+ *     2  u32 size          = blob bytes - 6
+ *     6  u32 L             = 51 + 16 n
+ *    10  tmp: u32 bitflags, i64 base_offset, max_offset, base_timestamp, max_timestamp,
+ *             u32 n + n x u32 relative_offset, u32 n + n x u32 relative_time (raw),
+ *             u32 n + n x u64 position, u8 monotonic, u8 with_offset, u8 non_data_timestamps
+ *  10+L  u32 CRC32C(tmp)   crc::crc32c, seed 0, as rpgpu_crc32c_extend
+ * Blob size = 65 + 16 n.  Plan: every row gets status, out_bytes and out_offset
+ * (an exclusive scan of the OK blobs with every start on a 16-byte boundary);
+ * d_totals[0] is the smallest out_cap that holds every OK blob.  A state whose
+ * envelope (59 + 16 n bytes) exceeds UINT32_MAX is RPGPU_SEGIDX_TOO_BIG
+ * (serde.h:539-541) and gets no blob.  Run: each blob whole, or not at all
+ * and RPGPU_SEGIDX_NO_ROOM; nothing outside the OK blobs and nothing at or past
+ * out_cap is written; a plan may be run any number of times, every run sets
+ * every OK / NO_ROOM status again.
+ *
+ * Hydrate, file i = bytes [blob_offset, blob_offset + blob_bytes) of d_files at
+ * any alignment, nothing outside is read; state i supplies entry_first and
+ * entry_cap ((blob_bytes - 53) / 16 always suffices) and, on OK only, receives
+ * the state and the entries; acc = 0, last_batch_max_timestamp = -1.  status:
+ * OK; REBUILD (materialize_index returns false: empty file or a
+ * serde::serde_exception); THROW (another exception escapes); NO_ROOM (more
+ * entries than entry_cap, `entries` = the need); COLUMNS_DIFFER (below).
+ * `reason` is the first event in the reference's order:
+ *   empty file                                     REBUILD  EMPTY_FILE
+ *   byte 0 < 3                                     REBUILD  UNSUPPORTED_VERSION
+ *   byte 0 == 3, legacy (index_state_serde_compat.h:46-101):
+ *       0 u8 3; 1 u32 size; 5 u64 checksum; 13 u32 bitflags; 17 four i64; 49 u32 n; 53 columns
+ *     fewer than 4 bytes for size (consume_type)   THROW    V3_SHORT
+ *     size != bytes after it                       REBUILD  V3_SIZE_MISMATCH
+ *     any later field or column short              THROW    V3_SHORT
+ *     XXH64(seed 0) of [13, 53 + 16 n) != checksum REBUILD  V3_CHECKSUM
+ *     bytes left after the columns                 REBUILD  TRAILING
+ *     -> monotonic = 0, with_offset = 0, non_data_timestamps = 0
+ *   otherwise the serde envelope (serde.h:592-647, index_state.cc:179-218):
+ *     fewer than 6 bytes                           REBUILD  HEADER_SHORT
+ *     bytes left < size (a smaller size is fine)   REBUILD  SIZE_BEYOND
+ *     byte 1 > 5                                   REBUILD  COMPAT_VERSION
+ *     fewer than 4 bytes for L                     REBUILD  TMP_LEN_SHORT
+ *     L > bytes left (share clamps, skip throws)   THROW    TMP_BEYOND
+ *     fewer than 4 bytes for the CRC               REBUILD  CRC_SHORT
+ *     CRC32C(tmp) != CRC                           REBUILD  CRC_MISMATCH
+ *     a field of tmp short (each column carries
+ *       its own count; byte 0 == 4 has no flags;
+ *       bytes of tmp behind the last field are
+ *       ignored)                                   REBUILD  FIELD_SHORT
+ *     bytes left after the CRC                     REBUILD  TRAILING
+ *     the three column counts differ               COLUMNS_DIFFER: the reference
+ *       accepts the blob and later indexes past the shorter columns (undefined
+ *       behaviour); here the caller rebuilds.  `entries` = the first count.
+ * The hashed length of a legacy blob is 40 + 16 n: a multiple of 8 and at least
+ * 40, so XXH64 runs its 32-byte stripe loop, the merge and 8-byte tail steps only.
+ *
+ * Find, one query per lane, restating the reference's loops (a hostile blob's
+ * columns need not be sorted); lower_bound is std::lower_bound's halving loop:
+ *   kind 0 find_nearest(offset o): o < base_offset or no entries -> NONE; needle =
+ *     (uint32)(o - base_offset) (truncating); it = lower_bound(relative_offset),
+ *     the last element if at the end; walk down to the first rel[i] <= needle.
+ *   kind 1 find_nearest(timestamp t): t < base_timestamp or no entries -> NONE;
+ *     raw = offset_time_index{t - base_timestamp, with_offset} (clamped); dist =
+ *     lower_bound(relative_time); the answer is entry max(dist - 1, 0), dist may
+ *     be n.  (The reference's end test compares iterators of two different
+ *     vectors and never holds: a non-empty index always answers.)  The caller
+ *     checks `monotonic` first (disk_log_impl.cc:1229).
+ *   kind 2 find_highest_timestamp_before(t): base_timestamp > t or no entries ->
+ *     NONE; from the last entry down, the first (int64)(uint32)offset_time() <
+ *     t - base_timestamp; timestamp = base_timestamp + offset_time(), ix; offset
+ *     and filepos 0.
+ *   offset = base_offset + relative_offset; timestamp = base_timestamp +
+ *   (uint32)offset_time(), offset_time() = raw - 2^31 as a uint32 when with_offset
+ *   (a negative stored delta comes back as a large positive one, as in the
+ *   reference).  A kind-0 answer seeds rpgpu_segment_read.offset += filepos.
+ *   Cost: on sorted columns kind 0 and kind 1 are the binary search plus at most
+ *   one step; kind 2 is the reference's linear scan from the last entry, O(n) by
+ *   design.  On a hostile state (unsorted or constant columns) the downward
+ *   walk of kind 0 is O(n) too: one lookup on a 2^28-entry state then reads
+ *   every entry on one lane, so bound entry_cap by what a segment can hold.
+ *
+ * Hand vectors.  State: base_offset 1000, max_offset 1159, base_timestamp T =
+ * 1700000000000, max_timestamp T + 9, with_offset 1, monotonic 1, non_data 0,
+ * entries (0, dt 0, 0), (48, dt 3, 49143), (96, dt 6, 98286).  Current format,
+ * 113 bytes, CRC 0a040bb7:
+ *   05046b0000006300000000000000e80300000000000087040000000000000068e5cf8b0100000968e5cf8b01
+ *   00000300000000000000300000006000000003000000000000800300008006000080030000000000000000000000
+ *   f7bf000000000000ee7f010000000000010100b70b040a
+ * Version 3, the same columns with with_offset 0 (raw times 0, 3, 6), 101 bytes,
+ * XXH64 fd40fabf14e63b1d:
+ *   03600000001d3be614bffa40fd00000000e80300000000000087040000000000000068e5cf8b0100000968e5cf8b
+ *   010000030000000000000030000000600000000000000003000000060000000000000000000000f7bf000000000000
+ *   ee7f010000000000
+ * XXH64, seed 0: "" ef46db3751d8e999, "abc" 44bc2cf5ad770999, bytes 0..99
+ * 6ac1e58032166597.  Lookups on the first state: offset 1047 -> entry 0 (1000,
+ * T, 0); 1048 -> entry 1 (1048, T + 3, 49143); 5000 -> entry 2; 999 -> NONE; time
+ * T + 3 -> entry 0; T -> entry 0; T + 100 -> entry 2; T - 1 -> NONE; before(T + 6)
+ * -> T + 3, ix 1; before(T) -> NONE. */
+typedef struct rpgpu_segidx_state {
+    int64_t base_offset, max_offset, base_timestamp, max_timestamp; /* index_state */
+    uint32_t bitflags;       /* index_state bitflags (unused by the broker)   */
+    uint32_t entries;        /* rows used at d_entries + entry_first          */
+    uint32_t entry_first, entry_cap; /* the state's slot in d_entries         */
+    uint64_t acc;            /* segment_index _acc                            */
+    int64_t last_batch_max_timestamp; /* segment_index _last_batch_max_timestamp */
+    uint8_t monotonic;       /* batch_timestamps_are_monotonic                */
+    uint8_t with_offset;     /* offset_delta_time                             */
+    uint8_t non_data_timestamps;
+    uint8_t reserved0;
+    uint32_t reserved1;
+    uint64_t reserved2;
+} rpgpu_segidx_state;        /* 80 bytes */
+
+typedef struct rpgpu_segidx_tracked {
+    int32_t status;          /* RPGPU_V_OK, RPGPU_V_INDEX_OFFSET_BELOW_BASE, _NON_DATA_ASSERT, _NO_ROOM, _BAD_STATE */
+    uint32_t tracked;        /* batches that went into the state              */
+    uint32_t added;          /* entries appended                              */
+    uint32_t reserved;
+} rpgpu_segidx_tracked;      /* 16 bytes */
+
+int32_t rpgpu_segidx_track_device(rpgpu_ctx* ctx, const rpgpu_batch_desc* d_descs,
+                                  const rpgpu_batch_result* d_results, uint32_t n, const rpgpu_segment* d_segs,
+                                  uint32_t nsegs, rpgpu_segidx_state* d_states, rpgpu_index_entry* d_entries,
+                                  uint64_t nentries, rpgpu_segidx_tracked* d_tracked, void* hip_stream);
+
+enum rpgpu_segidx_status {
+    RPGPU_SEGIDX_OK = 0,
+    RPGPU_SEGIDX_NO_ROOM = 1,
+    RPGPU_SEGIDX_TOO_BIG = 2,        /* write: "envelope too big"                  */
+    RPGPU_SEGIDX_REBUILD = 3,        /* hydrate: materialize_index returns false   */
+    RPGPU_SEGIDX_THROW = 4,          /* hydrate: std::out_of_range escapes         */
+    RPGPU_SEGIDX_COLUMNS_DIFFER = 5, /* hydrate: engine-only, see above            */
+    RPGPU_SEGIDX_BAD_STATE = 6       /* a slot or a file outside the arrays given  */
+};
+enum rpgpu_segidx_reason {
+    RPGPU_SEGIDX_R_NONE = 0,
+    RPGPU_SEGIDX_R_EMPTY_FILE = 1,
+    RPGPU_SEGIDX_R_UNSUPPORTED_VERSION = 2,
+    RPGPU_SEGIDX_R_HEADER_SHORT = 3,
+    RPGPU_SEGIDX_R_SIZE_BEYOND = 4,
+    RPGPU_SEGIDX_R_COMPAT_VERSION = 5,
+    RPGPU_SEGIDX_R_TMP_LEN_SHORT = 6,
+    RPGPU_SEGIDX_R_TMP_BEYOND = 7,
+    RPGPU_SEGIDX_R_CRC_SHORT = 8,
+    RPGPU_SEGIDX_R_CRC_MISMATCH = 9,
+    RPGPU_SEGIDX_R_FIELD_SHORT = 10,
+    RPGPU_SEGIDX_R_TRAILING = 11,
+    RPGPU_SEGIDX_R_V3_SIZE_MISMATCH = 12,
+    RPGPU_SEGIDX_R_V3_SHORT = 13,
+    RPGPU_SEGIDX_R_V3_CHECKSUM = 14,
+    RPGPU_SEGIDX_R_COLUMNS_DIFFER = 15,
+    RPGPU_SEGIDX_R_ENTRY_CAP = 16,
+    RPGPU_SEGIDX_R_BAD_ROW = 17
+};
+
+typedef struct rpgpu_segidx_blob {
+    int32_t status;          /* OK, NO_ROOM (run), TOO_BIG, BAD_STATE         */
+    uint32_t entries;        /* the state's entries when it was planned       */
+    uint64_t out_bytes;      /* 65 + 16 entries (up to 2^32 + 1); 0 without a blob */
+    uint64_t out_offset;     /* the blob in d_out, 16-byte aligned            */
+    uint64_t reserved;
+} rpgpu_segidx_blob;         /* 32 bytes */
+
+int32_t rpgpu_segidx_write_plan_device(rpgpu_ctx* ctx, const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                       uint64_t nentries, rpgpu_segidx_blob* d_blobs, uint64_t* d_totals,
+                                       void* hip_stream);
+int32_t rpgpu_segidx_write_run_device(rpgpu_ctx* ctx, const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                      const rpgpu_index_entry* d_entries, uint64_t nentries,
+                                      rpgpu_segidx_blob* d_blobs, uint8_t* d_out, uint64_t out_cap,
+                                      void* hip_stream);
+
+typedef struct rpgpu_segidx_file {
+    uint64_t blob_offset;    /* the file's bytes in d_files                   */
+    uint64_t blob_bytes;
+} rpgpu_segidx_file;         /* 16 bytes */
+
+typedef struct rpgpu_segidx_hydrated {
+    int32_t status;          /* enum rpgpu_segidx_status                      */
+    int32_t reason;          /* enum rpgpu_segidx_reason                      */
+    uint32_t version;        /* byte 0 of the file (0 for an empty file)      */
+    uint32_t entries;        /* the first column count, once it was read      */
+} rpgpu_segidx_hydrated;     /* 16 bytes */
+
+int32_t rpgpu_segidx_hydrate_device(rpgpu_ctx* ctx, const uint8_t* d_files, uint64_t files_bytes,
+                                    const rpgpu_segidx_file* d_rows, uint32_t nfiles,
+                                    rpgpu_segidx_state* d_states, rpgpu_index_entry* d_entries,
+                                    uint64_t nentries, rpgpu_segidx_hydrated* d_hydrated, void* hip_stream);
+
+enum rpgpu_segidx_kind {
+    RPGPU_SEGIDX_BY_OFFSET = 0,      /* find_nearest(model::offset)               */
+    RPGPU_SEGIDX_BY_TIME = 1,        /* find_nearest(model::timestamp)            */
+    RPGPU_SEGIDX_TIME_BEFORE = 2     /* find_highest_timestamp_before             */
+};
+typedef struct rpgpu_segidx_query {
+    uint32_t state;          /* row of d_states                               */
+    uint32_t kind;           /* enum rpgpu_segidx_kind                        */
+    int64_t key;             /* the offset or the timestamp                   */
+} rpgpu_segidx_query;        /* 16 bytes */
+
+enum rpgpu_segidx_find_status { RPGPU_SEGIDX_FOUND = 0, RPGPU_SEGIDX_NONE = 1, RPGPU_SEGIDX_BAD_QUERY = 2 };
+typedef struct rpgpu_segidx_found { /* segment_index::entry */
+    int32_t status;          /* enum rpgpu_segidx_find_status                 */
+    uint32_t ix;             /* the entry                                     */
+    int64_t offset, timestamp;
+    uint64_t filepos;
+} rpgpu_segidx_found;        /* 32 bytes */
+
+int32_t rpgpu_segidx_find_device(rpgpu_ctx* ctx, const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                 const rpgpu_index_entry* d_entries, uint64_t nentries,
+                                 const rpgpu_segidx_query* d_queries, uint32_t nq, rpgpu_segidx_found* d_found,
+                                 void* hip_stream);
 
 #ifdef __cplusplus
 }

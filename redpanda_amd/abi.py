@@ -55,6 +55,10 @@ V_DECOMP_OVERFLOW = 34
 V_SET_HEADER_SHORT = 36
 V_INDEX_OFFSET_BELOW_BASE = 37
 V_REMOTE_DELTA_ASSERT = 38
+# 39, 41, 42: rpgpu_segidx_tracked.status only (rpgpu_segidx_track_device), never in a batch result row
+V_INDEX_NON_DATA_ASSERT = 39
+V_INDEX_NO_ROOM = 41
+V_INDEX_BAD_STATE = 42
 V_SKIPPED = 40
 
 VERDICT_NAMES = {v: k for k, v in globals().items() if k.startswith("V_") and isinstance(v, int)}
@@ -204,6 +208,32 @@ RSINDEX_FOUND_DTYPE = np.dtype([("status", "<i4"), ("from_write_buffer", "<u4"),
                                 ("kaf_offset", "<i8"), ("file_pos", "<i8"), ("reserved", "<u8")])
 assert RSINDEX_SEGMENT_DTYPE.itemsize == 48 and RSINDEX_RESULT_DTYPE.itemsize == 64
 assert RSINDEX_QUERY_DTYPE.itemsize == 32 and RSINDEX_FOUND_DTYPE.itemsize == 48
+# segment index life cycle (rpgpu_segidx_*)
+(SEGIDX_OK, SEGIDX_NO_ROOM, SEGIDX_TOO_BIG, SEGIDX_REBUILD, SEGIDX_THROW, SEGIDX_COLUMNS_DIFFER,
+ SEGIDX_BAD_STATE) = range(7)  # enum rpgpu_segidx_status
+(SEGIDX_R_NONE, SEGIDX_R_EMPTY_FILE, SEGIDX_R_UNSUPPORTED_VERSION, SEGIDX_R_HEADER_SHORT, SEGIDX_R_SIZE_BEYOND,
+ SEGIDX_R_COMPAT_VERSION, SEGIDX_R_TMP_LEN_SHORT, SEGIDX_R_TMP_BEYOND, SEGIDX_R_CRC_SHORT, SEGIDX_R_CRC_MISMATCH,
+ SEGIDX_R_FIELD_SHORT, SEGIDX_R_TRAILING, SEGIDX_R_V3_SIZE_MISMATCH, SEGIDX_R_V3_SHORT, SEGIDX_R_V3_CHECKSUM,
+ SEGIDX_R_COLUMNS_DIFFER, SEGIDX_R_ENTRY_CAP, SEGIDX_R_BAD_ROW) = range(18)  # enum rpgpu_segidx_reason
+SEGIDX_BY_OFFSET, SEGIDX_BY_TIME, SEGIDX_TIME_BEFORE = range(3)  # enum rpgpu_segidx_kind
+SEGIDX_FOUND, SEGIDX_NONE, SEGIDX_BAD_QUERY = range(3)  # rpgpu_segidx_found.status
+SEGIDX_STATE_DTYPE = np.dtype([("base_offset", "<i8"), ("max_offset", "<i8"), ("base_timestamp", "<i8"),
+                               ("max_timestamp", "<i8"), ("bitflags", "<u4"), ("entries", "<u4"),
+                               ("entry_first", "<u4"), ("entry_cap", "<u4"), ("acc", "<u8"),
+                               ("last_batch_max_timestamp", "<i8"), ("monotonic", "u1"), ("with_offset", "u1"),
+                               ("non_data_timestamps", "u1"), ("reserved0", "u1"), ("reserved1", "<u4"),
+                               ("reserved2", "<u8")])
+SEGIDX_TRACKED_DTYPE = np.dtype([("status", "<i4"), ("tracked", "<u4"), ("added", "<u4"), ("reserved", "<u4")])
+SEGIDX_BLOB_DTYPE = np.dtype([("status", "<i4"), ("entries", "<u4"), ("out_bytes", "<u8"), ("out_offset", "<u8"),
+                              ("reserved", "<u8")])
+SEGIDX_FILE_DTYPE = np.dtype([("blob_offset", "<u8"), ("blob_bytes", "<u8")])
+SEGIDX_HYDRATED_DTYPE = np.dtype([("status", "<i4"), ("reason", "<i4"), ("version", "<u4"), ("entries", "<u4")])
+SEGIDX_QUERY_DTYPE = np.dtype([("state", "<u4"), ("kind", "<u4"), ("key", "<i8")])
+SEGIDX_FOUND_DTYPE = np.dtype([("status", "<i4"), ("ix", "<u4"), ("offset", "<i8"), ("timestamp", "<i8"),
+                               ("filepos", "<u8")])
+assert SEGIDX_STATE_DTYPE.itemsize == 80 and SEGIDX_TRACKED_DTYPE.itemsize == 16 and SEGIDX_BLOB_DTYPE.itemsize == 32
+assert SEGIDX_FILE_DTYPE.itemsize == 16 and SEGIDX_HYDRATED_DTYPE.itemsize == 16
+assert SEGIDX_QUERY_DTYPE.itemsize == 16 and SEGIDX_FOUND_DTYPE.itemsize == 32
 INDEX_ENTRY_DTYPE = np.dtype([("relative_offset", "<u4"), ("relative_time", "<u4"), ("position", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 32 and SEGMENT_STATE_DTYPE.itemsize == 48 and INDEX_ENTRY_DTYPE.itemsize == 16
 assert INDEX_DTYPE.itemsize == 32 and RP_HEADER_DTYPE.itemsize == 61
@@ -351,6 +381,11 @@ def lib() -> C.CDLL:
         _sig(L.rpgpu_rsindex_plan_device, _i32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp)
         _sig(L.rpgpu_rsindex_run_device, _i32, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp)
         _sig(L.rpgpu_rsindex_find_device, _i32, _vp, _vp, _vp, _u32, _vp, _vp)
+        _sig(L.rpgpu_segidx_track_device, _i32, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp)
+        _sig(L.rpgpu_segidx_write_plan_device, _i32, _vp, _vp, _u32, _u64, _vp, _vp, _vp)
+        _sig(L.rpgpu_segidx_write_run_device, _i32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp)
+        _sig(L.rpgpu_segidx_hydrate_device, _i32, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _u64, _vp, _vp)
+        _sig(L.rpgpu_segidx_find_device, _i32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp)
         _LIB = L
     return _LIB
 
@@ -392,4 +427,6 @@ EXPORTED = [
     "rpgpu_append_scratch_bytes", "rpgpu_append_plan_device", "rpgpu_append_run_device",
     "rpgpu_rsindex_scratch_bytes", "rpgpu_rsindex_plan_device", "rpgpu_rsindex_run_device",
     "rpgpu_rsindex_find_device",
+    "rpgpu_segidx_track_device", "rpgpu_segidx_write_plan_device", "rpgpu_segidx_write_run_device",
+    "rpgpu_segidx_hydrate_device", "rpgpu_segidx_find_device",
 ]

@@ -490,6 +490,69 @@ int32_t rpgpu_rsindex_find_device(rpgpu_ctx* c, const uint8_t* d_blobs, const rp
     return RPGPU_OK;
 }
 
+int32_t rpgpu_segidx_track_device(rpgpu_ctx* c, const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_results,
+                                  uint32_t n, const rpgpu_segment* d_segs, uint32_t nsegs,
+                                  rpgpu_segidx_state* d_states, rpgpu_index_entry* d_entries, uint64_t nentries,
+                                  rpgpu_segidx_tracked* d_tracked, void* hip_stream) {
+    if (!c || (n && (!d_descs || !d_results)) || (nsegs && (!d_segs || !d_states || !d_tracked)) ||
+        (nentries && !d_entries))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_segidx_track(d_descs, d_results, n, d_segs, nsegs, d_states, d_entries, nentries,
+                                              d_tracked, s);
+    if (e != hipSuccess) return fail(c, e, "segment index track launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_segidx_write_plan_device(rpgpu_ctx* c, const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                       uint64_t nentries, rpgpu_segidx_blob* d_blobs, uint64_t* d_totals,
+                                       void* hip_stream) {
+    if (!c || !d_totals || (nstates && (!d_states || !d_blobs))) return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_segidx_write_plan(d_states, nstates, nentries, d_blobs, d_totals, s);
+    if (e != hipSuccess) return fail(c, e, "segment index write plan launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_segidx_write_run_device(rpgpu_ctx* c, const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                      const rpgpu_index_entry* d_entries, uint64_t nentries,
+                                      rpgpu_segidx_blob* d_blobs, uint8_t* d_out, uint64_t out_cap,
+                                      void* hip_stream) {
+    if (!c || (nstates && (!d_states || !d_blobs)) || (nentries && !d_entries) || (out_cap && !d_out))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_segidx_write_run(d_states, nstates, d_entries, nentries, d_blobs, d_out, out_cap,
+                                                  c->d_tables, s);
+    if (e != hipSuccess) return fail(c, e, "segment index write run launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_segidx_hydrate_device(rpgpu_ctx* c, const uint8_t* d_files, uint64_t files_bytes,
+                                    const rpgpu_segidx_file* d_rows, uint32_t nfiles, rpgpu_segidx_state* d_states,
+                                    rpgpu_index_entry* d_entries, uint64_t nentries,
+                                    rpgpu_segidx_hydrated* d_hydrated, void* hip_stream) {
+    if (!c || (nfiles && (!d_rows || !d_states || !d_hydrated)) || (files_bytes && !d_files) ||
+        (nentries && !d_entries))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_segidx_hydrate(d_files, files_bytes, d_rows, nfiles, d_states, d_entries, nentries,
+                                                d_hydrated, c->d_tables, s);
+    if (e != hipSuccess) return fail(c, e, "segment index hydrate launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_segidx_find_device(rpgpu_ctx* c, const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                 const rpgpu_index_entry* d_entries, uint64_t nentries,
+                                 const rpgpu_segidx_query* d_queries, uint32_t nq, rpgpu_segidx_found* d_found,
+                                 void* hip_stream) {
+    if (!c || (nq && (!d_queries || !d_found)) || (nstates && !d_states) || (nentries && !d_entries))
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_segidx_find(d_states, nstates, d_entries, nentries, d_queries, nq, d_found, s);
+    if (e != hipSuccess) return fail(c, e, "segment index find launch");
+    return RPGPU_OK;
+}
+
 int32_t rpgpu_batch_timequery_device(rpgpu_ctx* c, const rpgpu_batch_result* d_results, uint32_t n,
                                      const rpgpu_record_index* d_index, const rpgpu_timequery* d_queries,
                                      uint32_t nq, rpgpu_timequery_result* d_out, void* hip_stream) {

@@ -157,5 +157,23 @@ hipError_t launch_rsindex_run(const rpgpu_rsindex_segment* d_segs, uint32_t nseg
 hipError_t launch_rsindex_find(const uint8_t* d_blobs, const rpgpu_rsindex_query* d_queries, uint32_t nq,
                                rpgpu_rsindex_found* d_found, hipStream_t s);
 
+// ---- rpgpu_segidx.hip
+hipError_t launch_segidx_track(const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_res, uint32_t n,
+                               const rpgpu_segment* d_segs, uint32_t nsegs, rpgpu_segidx_state* d_states,
+                               rpgpu_index_entry* d_entries, uint64_t nentries, rpgpu_segidx_tracked* d_tracked,
+                               hipStream_t s);
+hipError_t launch_segidx_write_plan(const rpgpu_segidx_state* d_states, uint32_t nstates, uint64_t nentries,
+                                    rpgpu_segidx_blob* d_blobs, uint64_t* d_totals, hipStream_t s);
+hipError_t launch_segidx_write_run(const rpgpu_segidx_state* d_states, uint32_t nstates,
+                                   const rpgpu_index_entry* d_entries, uint64_t nentries, rpgpu_segidx_blob* d_blobs,
+                                   uint8_t* d_out, uint64_t out_cap, const uint32_t* d_tables, hipStream_t s);
+hipError_t launch_segidx_hydrate(const uint8_t* d_files, uint64_t files_bytes, const rpgpu_segidx_file* d_rows,
+                                 uint32_t nfiles, rpgpu_segidx_state* d_states, rpgpu_index_entry* d_entries,
+                                 uint64_t nentries, rpgpu_segidx_hydrated* d_hydrated, const uint32_t* d_tables,
+                                 hipStream_t s);
+hipError_t launch_segidx_find(const rpgpu_segidx_state* d_states, uint32_t nstates, const rpgpu_index_entry* d_entries,
+                              uint64_t nentries, const rpgpu_segidx_query* d_queries, uint32_t nq,
+                              rpgpu_segidx_found* d_found, hipStream_t s);
+
 }  // namespace rpgpu
 #endif

@@ -813,6 +813,132 @@ class Engine:
         torch.cuda.synchronize(dev)
         return d_found.cpu().numpy().view(abi.RSINDEX_FOUND_DTYPE)[:nq].copy()
 
+    # -- segment index life cycle (rpgpu_segidx_*) --------------------------------------
+    def _segidx_up(self, states: np.ndarray, entries: np.ndarray, guard: int = 0):
+        """State rows and the shared entry array on the device; `guard` more entry
+        rows of 0xA5 behind the array (outside nentries)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        states = np.ascontiguousarray(states, dtype=abi.SEGIDX_STATE_DTYPE)
+        entries = np.ascontiguousarray(entries, dtype=abi.INDEX_ENTRY_DTYPE)
+        raw = np.concatenate([entries.view(np.uint8).reshape(-1), np.full(16 * max(guard, 1), 0xA5, np.uint8)])
+        d_states = torch.from_numpy(states.view(np.uint8).reshape(-1).copy() if len(states)
+                                    else np.zeros(80, np.uint8)).to(dev)
+        return dev, len(states), len(entries), d_states, torch.from_numpy(raw).to(dev)
+
+    @staticmethod
+    def _segidx_down(d_states, ns: int, d_entries, ne: int, guard: int) -> dict:
+        return dict(states=d_states.cpu().numpy().view(abi.SEGIDX_STATE_DTYPE)[:ns].copy(),
+                    entries=d_entries.cpu().numpy().view(abi.INDEX_ENTRY_DTYPE)[:ne + guard].copy())
+
+    def segidx_track(self, descs: np.ndarray, results: np.ndarray, segs: np.ndarray, states: np.ndarray,
+                     entries: np.ndarray, guard: int = 0) -> dict:
+        """rpgpu_segidx_track_device: segment row s (SEGMENT_DTYPE) over validated
+        result rows continues state s (SEGIDX_STATE_DTYPE) in the shared entry array.
+        Returns host copies: states, entries (then `guard` rows that must still
+        hold 0xA5), tracked (SEGIDX_TRACKED_DTYPE)."""
+        import torch
+
+        dev, ns, ne, d_states, d_entries = self._segidx_up(states, entries, guard)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        descs = np.ascontiguousarray(descs, dtype=abi.DESC_DTYPE)
+        results = np.ascontiguousarray(results, dtype=abi.RESULT_DTYPE)
+        segs = np.ascontiguousarray(segs, dtype=abi.SEGMENT_DTYPE)
+        if len(results) != len(descs) or len(segs) != ns:
+            raise ValueError("one result row per descriptor, one state per segment")
+
+        def up(a):
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy() if a.size else np.zeros(64, np.uint8)).to(dev)
+
+        d_descs, d_res, d_segs = up(descs), up(results), up(segs)
+        d_trk = torch.full((max(ns, 1) * 16,), 0xA5, dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_segidx_track_device(self._ctx, d_descs.data_ptr(), d_res.data_ptr(), len(descs),
+                                                 d_segs.data_ptr(), ns, d_states.data_ptr(), d_entries.data_ptr(),
+                                                 ne, d_trk.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_segidx_track_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        out = self._segidx_down(d_states, ns, d_entries, ne, guard)
+        out["tracked"] = d_trk.cpu().numpy().view(abi.SEGIDX_TRACKED_DTYPE)[:ns].copy()
+        return out
+
+    def segidx_write(self, states: np.ndarray, entries: np.ndarray, out_cap: int | None = None, plans: int = 1,
+                     runs: int = 1, fill: int | None = None, guard: int = 0) -> dict:
+        """rpgpu_segidx_write_plan_device / rpgpu_segidx_write_run_device: every
+        state as the bytes of serde::to_iobuf(index_state).  Returns host copies:
+        plan_blobs (SEGIDX_BLOB_DTYPE after the plan), blobs (after the run),
+        totals (the plan's one), out (out_cap bytes, the plan's total by default,
+        then `guard` more; pre-filled with `fill` when given, else zero) and out_cap."""
+        import torch
+
+        dev, ns, ne, d_states, d_entries = self._segidx_up(states, entries)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        d_blobs = torch.zeros(max(ns, 1) * 32, dtype=torch.uint8, device=dev)
+        d_tot = torch.zeros(1, dtype=torch.int64, device=dev)
+        for _ in range(plans):
+            rc = self._lib.rpgpu_segidx_write_plan_device(self._ctx, d_states.data_ptr(), ns, ne, d_blobs.data_ptr(),
+                                                          d_tot.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_segidx_write_plan_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        totals = d_tot.cpu().numpy().astype(np.uint64)
+        plan_blobs = d_blobs.cpu().numpy().view(abi.SEGIDX_BLOB_DTYPE)[:ns].copy()
+        out_cap = int(totals[0]) if out_cap is None else out_cap
+        d_out = torch.full((max(out_cap + guard, 1),), 0 if fill is None else fill, dtype=torch.uint8, device=dev)
+        for _ in range(runs):
+            rc = self._lib.rpgpu_segidx_write_run_device(self._ctx, d_states.data_ptr(), ns, d_entries.data_ptr(), ne,
+                                                         d_blobs.data_ptr(), d_out.data_ptr(), out_cap, sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_segidx_write_run_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return dict(plan_blobs=plan_blobs, blobs=d_blobs.cpu().numpy().view(abi.SEGIDX_BLOB_DTYPE)[:ns].copy(),
+                    totals=totals, out=d_out.cpu().numpy()[: out_cap + guard].copy(), out_cap=out_cap)
+
+    def segidx_hydrate(self, files: np.ndarray, rows: np.ndarray, states: np.ndarray, entries: np.ndarray,
+                       guard: int = 0) -> dict:
+        """rpgpu_segidx_hydrate_device: materialize_index_from_file per row
+        (SEGIDX_FILE_DTYPE over the bytes of `files`; the device buffer holds
+        exactly those bytes).  State i supplies entry_first / entry_cap.  Returns
+        host copies: states, entries (then `guard` rows of 0xA5), hydrated."""
+        import torch
+
+        dev, ns, ne, d_states, d_entries = self._segidx_up(states, entries, guard)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        files = np.ascontiguousarray(files, dtype=np.uint8)
+        rows = np.ascontiguousarray(rows, dtype=abi.SEGIDX_FILE_DTYPE)
+        if len(rows) != ns:
+            raise ValueError("one state per file")
+        d_files = torch.from_numpy(files.copy() if files.size else np.zeros(1, np.uint8)).to(dev)
+        d_rows = torch.from_numpy(rows.view(np.uint8).reshape(-1).copy() if ns else np.zeros(16, np.uint8)).to(dev)
+        d_hyd = torch.full((max(ns, 1) * 16,), 0xA5, dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_segidx_hydrate_device(self._ctx, d_files.data_ptr(), files.size, d_rows.data_ptr(), ns,
+                                                   d_states.data_ptr(), d_entries.data_ptr(), ne, d_hyd.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_segidx_hydrate_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        out = self._segidx_down(d_states, ns, d_entries, ne, guard)
+        out["hydrated"] = d_hyd.cpu().numpy().view(abi.SEGIDX_HYDRATED_DTYPE)[:ns].copy()
+        return out
+
+    def segidx_find(self, states: np.ndarray, entries: np.ndarray, queries: np.ndarray) -> np.ndarray:
+        """rpgpu_segidx_find_device: find_nearest(offset), find_nearest(timestamp)
+        or find_highest_timestamp_before per query (SEGIDX_QUERY_DTYPE)."""
+        import torch
+
+        dev, ns, ne, d_states, d_entries = self._segidx_up(states, entries)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        queries = np.ascontiguousarray(queries, dtype=abi.SEGIDX_QUERY_DTYPE)
+        nq = len(queries)
+        d_q = torch.from_numpy(queries.view(np.uint8).reshape(-1).copy() if nq else np.zeros(16, np.uint8)).to(dev)
+        d_found = torch.full((max(nq, 1) * 32,), 0xA5, dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_segidx_find_device(self._ctx, d_states.data_ptr(), ns, d_entries.data_ptr(), ne,
+                                                d_q.data_ptr(), nq, d_found.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_segidx_find_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return d_found.cpu().numpy().view(abi.SEGIDX_FOUND_DTYPE)[:nq].copy()
+
     def batch_timequery(self, results: np.ndarray, index: np.ndarray, queries: np.ndarray) -> np.ndarray:
         """rpgpu_batch_timequery_device (storage::batch_timequery) per query."""
         import torch
