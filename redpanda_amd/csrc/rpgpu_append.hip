@@ -87,11 +87,6 @@ uint32_t sort_passes(uint32_t nlogs) {
     return (bits + 7) / 8;
 }
 
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
-    const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 __global__ __launch_bounds__(256) void append_classify_kernel(const rpgpu_batch_desc* __restrict__ descs,
                                                               const rpgpu_batch_result* __restrict__ res, uint32_t n,
                                                               const int32_t* __restrict__ codes,
@@ -196,7 +191,7 @@ __global__ __launch_bounds__(256) void append_walk_kernel(const rpgpu_batch_desc
                                                           uint64_t* __restrict__ dst,
                                                           rpgpu_append_segment* __restrict__ segs,
                                                           rpgpu_append_log_result* __restrict__ lres) {
-    const uint32_t log = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t log = wave_item();
     if (log >= nlogs) return;
     const uint32_t l = lane_id();
     const rpgpu_append_log lg = logs[log];
@@ -502,12 +497,6 @@ __global__ __launch_bounds__(256) void append_write_kernel(
     }
 }
 
-#define AP_CHECK()                                  \
-    do {                                            \
-        hipError_t e_ = hipGetLastError();          \
-        if (e_ != hipSuccess) return e_;            \
-    } while (0)
-
 }  // namespace
 
 size_t append_scratch_bytes(uint32_t n, uint32_t nlogs) { return ap_layout(nullptr, n, nlogs, nullptr); }
@@ -525,31 +514,31 @@ hipError_t launch_append_plan(const rpgpu_batch_desc* d_descs, const rpgpu_batch
     if (n) {
         append_classify_kernel<<<(n + 255) / 256, 256, 0, s>>>(d_descs, d_res, n, d_codes, d_logs, part_lo, nlogs,
                                                                p.key, p.starts, d_rows);
-        AP_CHECK();
+        RPGPU_LAUNCH_CHECK();
     }
     if (nlogs == 0) return hipSuccess;
     append_scan_kernel<<<1, kScanBlock, 0, s>>>(p.starts, nlogs + 1);
-    AP_CHECK();
+    RPGPU_LAUNCH_CHECK();
     const uint32_t passes = sort_passes(nlogs), nb = sort_blocks(n);
     const uint32_t* in = nullptr;
     for (uint32_t k = 0; n && k < passes; k++) {
         uint32_t* out = (k & 1) ? p.idx_b : p.idx_a;
         append_hist_kernel<<<nb, kSortBlock, 0, s>>>(p.key, in, n, 8 * k, nb, p.table);
-        AP_CHECK();
+        RPGPU_LAUNCH_CHECK();
         append_scan_kernel<<<1, kScanBlock, 0, s>>>(p.table, nb * 256);
-        AP_CHECK();
+        RPGPU_LAUNCH_CHECK();
         append_scatter_kernel<<<nb, kSortBlock, 0, s>>>(p.key, in, n, 8 * k, nb, p.table, out);
-        AP_CHECK();
+        RPGPU_LAUNCH_CHECK();
         in = out;
     }
-    append_walk_kernel<<<(uint32_t)(((uint64_t)nlogs + 3) / 4), 256, 0, s>>>(d_descs, d_res, d_logs, nlogs, in,
-                                                                             p.starts, d_rows, p.dst, p.segs, d_lres);
-    AP_CHECK();
+    append_walk_kernel<<<wave_grid(nlogs), 256, 0, s>>>(d_descs, d_res, d_logs, nlogs, in, p.starts, d_rows, p.dst,
+                                                        p.segs, d_lres);
+    RPGPU_LAUNCH_CHECK();
     append_log_scan_kernel<<<1, kScanThreads, 0, s>>>(d_lres, nlogs, d_totals);
-    AP_CHECK();
+    RPGPU_LAUNCH_CHECK();
     if (n) {
         append_fixup_kernel<<<(n + 255) / 256, 256, 0, s>>>(p.key, n, nlogs, d_lres, d_rows, p.dst);
-        AP_CHECK();
+        RPGPU_LAUNCH_CHECK();
     }
     return hipSuccess;
 }
@@ -571,7 +560,7 @@ hipError_t launch_append_run(const uint8_t* d_data, const rpgpu_batch_desc* d_de
     const uint32_t waves = items < 65536u ? items : 65536u;
     append_write_kernel<<<(waves + 3) / 4, 256, 0, s>>>(d_data, d_descs, d_res, n, part_lo, nlogs, d_rows, d_lres,
                                                         p.dst, d_tables, d_out, d_out_descs, d_out_res, r);
-    AP_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 

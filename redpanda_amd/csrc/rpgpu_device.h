@@ -51,6 +51,11 @@ __device__ __forceinline__ uint32_t lane_id() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(r));
     return r;
 }
+// one wavefront per item: the launch's wavefront number as a wave-uniform
+// value, in a grid of wave_grid(n) workgroups (rpgpu_launch.h)
+__device__ __forceinline__ uint32_t wave_item() {
+    return __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+}
 __device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) { return __builtin_amdgcn_readlane(v, l); }
 // v with lane L replaced by the wave-uniform value s
 template <class S>
@@ -103,6 +108,12 @@ struct Img64 {
 };
 
 // ---------------------------------------------------------- CRC primitives
+// the table blob of either polynomial into LDS, by the whole workgroup (a barrier)
+__device__ __forceinline__ void load_tables(uint32_t* sT, const uint32_t* tables) {
+    for (int i = threadIdx.x; i < kTableWords / 4; i += blockDim.x)
+        reinterpret_cast<u32x4*>(sT)[i] = reinterpret_cast<const u32x4*>(tables)[i];
+    __syncthreads();
+}
 // byte SEL of x, shifted left (L) or right (R) by 2, in one SDWA VALU op.
 // On x & 0x0F0F0F0F (L) and x & 0xF0F0F0F0 (R) both give a nibble * 4, i.e.
 // the byte offset of a 16-entry table word.

@@ -100,12 +100,6 @@ __device__ __forceinline__ void store_result(rpgpu_batch_result* out, uint32_t r
     if (l < 16) reinterpret_cast<uint32_t*>(out)[l] = rv;
 }
 
-__device__ __forceinline__ void load_tables(uint32_t* s, const uint32_t* __restrict__ g) {
-    for (int i = threadIdx.x; i < kTableWords / 4; i += blockDim.x)
-        reinterpret_cast<u32x4*>(s)[i] = reinterpret_cast<const u32x4*>(g)[i];
-    __syncthreads();
-}
-
 // header CRC over image D[4..61) (internal_header_only_crc,
 // record_utils.cc:34-55), D given one dword per lane (lanes 0..15 of dv):
 // the 64-byte right-aligned window [7 zero bytes | D[4..61)], init folded

@@ -9,7 +9,17 @@
 
 #include "rpgpu_internal.h"
 
+// after a kernel launch, inside a launcher: return the launch's error, if any
+#define RPGPU_LAUNCH_CHECK()                        \
+    do {                                            \
+        hipError_t e_ = hipGetLastError();          \
+        if (e_ != hipSuccess) return e_;            \
+    } while (0)
+
 namespace rpgpu {
+
+// workgroups of 256 threads for one wavefront per item (wave_item, rpgpu_device.h)
+inline uint32_t wave_grid(uint32_t n) { return (uint32_t)(((uint64_t)n + 3) / 4); }
 
 // ---- rpgpu_kernels.hip
 hipError_t launch_validate(const rpgpu_batch_desc* d_descs, uint32_t n, const uint8_t* d_data,

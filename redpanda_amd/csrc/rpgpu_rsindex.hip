@@ -74,10 +74,6 @@ __host__ __device__ inline size_t rs_layout(void* p, uint32_t n, uint32_t nsegs,
     return o;
 }
 
-__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
-    const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m) {
     const uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
     return ((uint64_t)hi << 32) | lo;
@@ -104,6 +100,7 @@ __global__ __launch_bounds__(256) void rsindex_select_kernel(const uint8_t* __re
                                                              const rpgpu_rsindex_segment* __restrict__ segs,
                                                              uint32_t nsegs, rpgpu_rsindex_result* __restrict__ results,
                                                              void* scratch) {
+    // wave_item() written out: through the call, the `seg == 0 && l == 0` test below compiles differently
     const uint32_t seg = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     if (seg >= nsegs) return;
     const uint32_t l = lane_id();
@@ -212,7 +209,7 @@ __device__ __forceinline__ RsDeltas row_deltas(const RsParts& p, const rpgpu_rsi
 __global__ __launch_bounds__(256) void rsindex_width_kernel(const rpgpu_rsindex_segment* __restrict__ segs,
                                                             uint32_t nsegs, rpgpu_rsindex_result* __restrict__ results,
                                                             void* scratch, uint32_t n) {
-    const uint32_t seg = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t seg = wave_item();
     if (seg >= nsegs) return;
     const uint32_t l = lane_id(), e = l & 15u;
     RsParts p;
@@ -278,7 +275,7 @@ __global__ __launch_bounds__(kScanBlock) void rsindex_place_kernel(rpgpu_rsindex
 __global__ __launch_bounds__(256) void rsindex_emit_kernel(const rpgpu_rsindex_segment* __restrict__ segs,
                                                            uint32_t nsegs, rpgpu_rsindex_result* __restrict__ results,
                                                            uint8_t* __restrict__ out, uint64_t out_cap, void* scratch) {
-    const uint32_t seg = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t seg = wave_item();
     if (seg >= nsegs) return;
     const uint32_t l = lane_id(), e = l & 15u;
     RsParts p;
@@ -450,7 +447,7 @@ __device__ __forceinline__ bool scan_stream(const uint8_t* s, uint32_t len, uint
 __global__ __launch_bounds__(256) void rsindex_find_kernel(const uint8_t* __restrict__ blobs,
                                                            const rpgpu_rsindex_query* __restrict__ queries, uint32_t nq,
                                                            rpgpu_rsindex_found* __restrict__ found) {
-    const uint32_t qi = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t qi = wave_item();
     if (qi >= nq) return;
     const uint32_t l = lane_id();
     const rpgpu_rsindex_query q = queries[qi];
@@ -497,12 +494,6 @@ __global__ __launch_bounds__(256) void rsindex_find_kernel(const uint8_t* __rest
     if (l == 0) found[qi] = o;
 }
 
-#define RS_CHECK()                                  \
-    do {                                            \
-        hipError_t e_ = hipGetLastError();          \
-        if (e_ != hipSuccess) return e_;            \
-    } while (0)
-
 }  // namespace
 
 size_t rsindex_scratch_bytes(uint32_t n, uint32_t nsegs) { return rs_layout(nullptr, n, nsegs, nullptr); }
@@ -515,30 +506,29 @@ hipError_t launch_rsindex_plan(const uint8_t* d_data, const rpgpu_batch_desc* d_
     if (nsegs == 0) return hipSuccess;
     RsParts p;
     rs_layout(d_scratch, n, nsegs, &p);
-    const uint32_t grid = (uint32_t)(((uint64_t)nsegs + 3) / 4);
+    const uint32_t grid = wave_grid(nsegs);
     rsindex_select_kernel<<<grid, 256, 0, s>>>(d_data, d_descs, n, d_segs, nsegs, d_results, d_scratch);
-    RS_CHECK();
+    RPGPU_LAUNCH_CHECK();
     rsindex_width_kernel<<<grid, 256, 0, s>>>(d_segs, nsegs, d_results, d_scratch, n);
-    RS_CHECK();
+    RPGPU_LAUNCH_CHECK();
     rsindex_place_kernel<<<1, kScanBlock, 0, s>>>(d_results, nsegs, p.place, d_totals);
-    RS_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 hipError_t launch_rsindex_run(const rpgpu_rsindex_segment* d_segs, uint32_t nsegs, rpgpu_rsindex_result* d_results,
                               uint8_t* d_out, uint64_t out_cap, void* d_scratch, hipStream_t s) {
     if (nsegs == 0) return hipSuccess;
-    rsindex_emit_kernel<<<(uint32_t)(((uint64_t)nsegs + 3) / 4), 256, 0, s>>>(d_segs, nsegs, d_results, d_out, out_cap,
-                                                                             d_scratch);
-    RS_CHECK();
+    rsindex_emit_kernel<<<wave_grid(nsegs), 256, 0, s>>>(d_segs, nsegs, d_results, d_out, out_cap, d_scratch);
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 hipError_t launch_rsindex_find(const uint8_t* d_blobs, const rpgpu_rsindex_query* d_queries, uint32_t nq,
                                rpgpu_rsindex_found* d_found, hipStream_t s) {
     if (nq == 0) return hipSuccess;
-    rsindex_find_kernel<<<(uint32_t)(((uint64_t)nq + 3) / 4), 256, 0, s>>>(d_blobs, d_queries, nq, d_found);
-    RS_CHECK();
+    rsindex_find_kernel<<<wave_grid(nq), 256, 0, s>>>(d_blobs, d_queries, nq, d_found);
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 

@@ -26,6 +26,11 @@ __device__ __forceinline__ uint64_t shfl_up(uint64_t x, int s) {
     const uint32_t lo = __shfl_up((uint32_t)x, s, 64), hi = __shfl_up((uint32_t)(x >> 32), s, 64);
     return ((uint64_t)hi << 32) | lo;
 }
+// every lane receives lane src's value
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
+    const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
+    return ((uint64_t)hi << 32) | lo;
+}
 
 // inclusive scan over the wave's lanes (wrapping).  T: uint32_t, uint64_t, or
 // a type with operator+ and a shfl_up of its own.

@@ -49,17 +49,6 @@ static_assert(sizeof(rpgpu_segidx_state) == 80 && sizeof(rpgpu_segidx_tracked) =
                   sizeof(rpgpu_segidx_found) == 32 && sizeof(rpgpu_index_entry) == 16,
               "segment index row layouts");
 
-__device__ __forceinline__ uint64_t bcast64(uint64_t v, int src) {
-    const uint32_t lo = __shfl((uint32_t)v, src, 64), hi = __shfl((uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ void load_tables(uint32_t* sT, const uint32_t* __restrict__ tables) {
-    for (int i = threadIdx.x; i < kTableWords / 4; i += blockDim.x)
-        reinterpret_cast<u32x4*>(sT)[i] = reinterpret_cast<const u32x4*>(tables)[i];
-    __syncthreads();
-}
-
 // segment_index::maybe_track per segment, from the segment's state
 __global__ __launch_bounds__(256) void segidx_track_kernel(const rpgpu_batch_desc* __restrict__ descs,
                                                            const rpgpu_batch_result* __restrict__ res, uint32_t n,
@@ -145,7 +134,7 @@ __global__ __launch_bounds__(256) void segidx_emit_kernel(const rpgpu_segidx_sta
                                                           const rpgpu_index_entry* __restrict__ entries,
                                                           uint64_t nentries, rpgpu_segidx_blob* __restrict__ blobs,
                                                           uint8_t* __restrict__ out, uint64_t out_cap) {
-    const uint32_t si = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t si = wave_item();
     if (si >= nstates) return;
     const uint32_t l = lane_id();
     const rpgpu_segidx_blob b = blobs[si];
@@ -193,7 +182,7 @@ __global__ __launch_bounds__(kValidateThreads) void segidx_crc_kernel(const rpgp
                                                                       const uint32_t* __restrict__ tables) {
     __shared__ __attribute__((aligned(16))) uint32_t sT[kTableWords];
     load_tables(sT, tables);
-    const uint32_t si = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t si = wave_item();
     if (si >= nstates) return;
     const uint32_t l = lane_id();
     const rpgpu_segidx_blob b = blobs[si];
@@ -211,7 +200,7 @@ __global__ __launch_bounds__(kValidateThreads) void segidx_hydrate_kernel(
     rpgpu_segidx_hydrated* __restrict__ hydrated, const uint32_t* __restrict__ tables) {
     __shared__ __attribute__((aligned(16))) uint32_t sT[kTableWords];
     load_tables(sT, tables);
-    const uint32_t fi = __builtin_amdgcn_readfirstlane((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const uint32_t fi = wave_item();
     if (fi >= nfiles) return;
     const uint32_t l = lane_id();
     const rpgpu_segidx_file row = rows[fi];
@@ -228,7 +217,7 @@ __global__ __launch_bounds__(kValidateThreads) void segidx_hydrate_kernel(
         if (v.legacy) {
             // the hashed length is 40 + 16 n: xxh_ok holds (rpgpu_segidx.h asserts it)
             const uint64_t mine = l < 4 ? rpsx::xxh_lane(p + v.sum_at, v.sum_len, l) : 0;
-            const uint64_t acc[4] = {bcast64(mine, 0), bcast64(mine, 1), bcast64(mine, 2), bcast64(mine, 3)};
+            const uint64_t acc[4] = {shfl64(mine, 0), shfl64(mine, 1), shfl64(mine, 2), shfl64(mine, 3)};
             sum = rpsx::xxh_finish(acc, p + v.sum_at, v.sum_len);
         } else {
             sum = crc_range_wave(sT, p + v.sum_at, (int64_t)v.sum_len, ~0u, l);
@@ -270,14 +259,6 @@ __global__ __launch_bounds__(256) void segidx_find_kernel(const rpgpu_segidx_sta
     found[qi] = o;
 }
 
-#define SX_CHECK()                                  \
-    do {                                            \
-        hipError_t e_ = hipGetLastError();          \
-        if (e_ != hipSuccess) return e_;            \
-    } while (0)
-
-inline uint32_t wave_grid(uint32_t n) { return (uint32_t)(((uint64_t)n + 3) / 4); }
-
 }  // namespace
 
 hipError_t launch_segidx_track(const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_res, uint32_t n,
@@ -287,14 +268,14 @@ hipError_t launch_segidx_track(const rpgpu_batch_desc* d_descs, const rpgpu_batc
     if (nsegs == 0) return hipSuccess;
     segidx_track_kernel<<<(nsegs + 255) / 256, 256, 0, s>>>(d_descs, d_res, n, d_segs, nsegs, d_states, d_entries,
                                                            nentries, d_tracked);
-    SX_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 hipError_t launch_segidx_write_plan(const rpgpu_segidx_state* d_states, uint32_t nstates, uint64_t nentries,
                                     rpgpu_segidx_blob* d_blobs, uint64_t* d_totals, hipStream_t s) {
     segidx_place_kernel<<<1, kScanBlock, 0, s>>>(d_states, nstates, nentries, d_blobs, d_totals);
-    SX_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 
@@ -304,9 +285,9 @@ hipError_t launch_segidx_write_run(const rpgpu_segidx_state* d_states, uint32_t 
     if (nstates == 0) return hipSuccess;
     segidx_emit_kernel<<<wave_grid(nstates), 256, 0, s>>>(d_states, nstates, d_entries, nentries, d_blobs, d_out,
                                                           out_cap);
-    SX_CHECK();
+    RPGPU_LAUNCH_CHECK();
     segidx_crc_kernel<<<wave_grid(nstates), kValidateThreads, 0, s>>>(d_blobs, nstates, d_out, d_tables);
-    SX_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 
@@ -317,7 +298,7 @@ hipError_t launch_segidx_hydrate(const uint8_t* d_files, uint64_t files_bytes, c
     if (nfiles == 0) return hipSuccess;
     segidx_hydrate_kernel<<<wave_grid(nfiles), kValidateThreads, 0, s>>>(d_files, files_bytes, d_rows, nfiles, d_states,
                                                                          d_entries, nentries, d_hydrated, d_tables);
-    SX_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 
@@ -326,7 +307,7 @@ hipError_t launch_segidx_find(const rpgpu_segidx_state* d_states, uint32_t nstat
                               rpgpu_segidx_found* d_found, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     segidx_find_kernel<<<(nq + 255) / 256, 256, 0, s>>>(d_states, nstates, d_entries, nentries, d_queries, nq, d_found);
-    SX_CHECK();
+    RPGPU_LAUNCH_CHECK();
     return hipSuccess;
 }
 

@@ -8,6 +8,8 @@ batch; a config batch indexed first then overwritten by the fir
 data batch's timestamps; the monotonic flag; the base-offset vassert; a bad batch
 ends recovery).  The GPU test compares rpgpu_segment_index_device with the oracle."""
 import os
+import re
+import subprocess
 import sys
 
 import numpy as np
@@ -77,6 +79,28 @@ def test_vassert_and_bad_batch_stop():
     _, descs, res, segs = segment(bs)
     st, _ = orc.segment_index(descs, res, segs)
     assert st[0]["status"] == 0 and st[0]["tracked"] == 1
+
+
+def test_kernel_keeps_its_state_in_registers(tmp_path):
+    """The compiler's own resource remarks for rpgpu_index.hip (DESIGN.md §3 states the numbers): the
+    index state of a segment stays in registers for the whole scan."""
+    from redpanda_amd import _build
+
+    r = subprocess.run(["hipcc", *_build.rpgpu_flags(), "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                        "-c", str(_build.CSRC / "rpgpu_index.hip"), "-o", str(tmp_path / "ix.o")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    kernels, cur = {}, None
+    for line in r.stderr.splitlines():
+        m = re.search(r"remark: \s*([A-Za-z][A-Za-z /\[\]]*?):\s*(\S+)", line)
+        if m and m.group(1).strip() == "Function Name":
+            cur = kernels.setdefault(m.group(2), {})
+        elif m and cur is not None and m.group(2).isdigit():
+            cur[m.group(1).strip()] = int(m.group(2))
+    assert len(kernels) == 1 and "segment_index_kernel" in next(iter(kernels))
+    u = next(iter(kernels.values()))
+    assert u["ScratchSize [bytes/lane]"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, u
+    assert u["AGPRs"] == 0 and u["VGPRs"] <= 64 and u["Occupancy [waves/SIMD]"] == 8, u
 
 
 @pytest.mark.gpu

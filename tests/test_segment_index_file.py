@@ -3,7 +3,7 @@
 * the Python model tests/segment_index_file.py against the hand vectors of
   include/rpgpu.h (blob bytes, CRC, XXH64, lookups), its XXH64 against the xxhash
   module, its track against the untouched oracle on the cases of
-  tests/test_segment_index.py, and the split property: tracking [0, k) then
+  tests/test_segment_index.py and on random segments, and the split property: tracking [0, k) then
   [k, 12) equals tracking all 12;
 * every hydrate outcome once, by name, against a table traced in the reference;
 * the shared core redpanda_amd/csrc/rpgpu_segidx.h compiled for the host
@@ -13,6 +13,7 @@
 * struct sizes, offsets and enum values of include/rpgpu.h against redpanda_amd/abi.py;
 * the compiler's resource remarks for the kernels: no scratch, no spills.
 The device half is tests/test_gpu_segment_index_file.py."""
+import functools
 import os
 import re
 import subprocess
@@ -106,17 +107,40 @@ def split_cases():
             "config_first": segment(config, base_offset=100, with_offset=True)}
 
 
+@functools.lru_cache(maxsize=None)
+def random_cases(seed=23, count=60):
+    """Segments of 0-12 small batches as recovery may meet them: a third of the batches no user data,
+    now and then a base offset below the segment's or a bad CRC, every topic kind, time format and step.
+    Built once; nobody writes to them."""
+    rng = np.random.default_rng(seed)
+    cases = []
+    for _ in range(count):
+        base, bs = int(rng.integers(0, 1000)), []
+        off = base
+        for _ in range(int(rng.integers(0, 13))):
+            ts = 1_700_000_000_000 + int(rng.integers(-5_000_000, 5_000_000))
+            bs.append(disk_batch(off if rng.integers(0, 25) else base - 1, nrec=int(rng.integers(1, 4)),
+                                 vlen=int(rng.integers(0, 3000)), first_ts=ts,
+                                 max_ts=ts + int(rng.integers(-10, 100_000)),
+                                 btype=1 if rng.integers(0, 3) else int(rng.integers(2, 6)),
+                                 crc=None if rng.integers(0, 40) else 1))
+            off += int(rng.integers(1, 40))
+        cases.append(segment(bs, base_offset=base, internal=bool(rng.integers(0, 2)),
+                             with_offset=bool(rng.integers(0, 2)), step=int(rng.choice([1, 4096, 32768]))))
+    return tuple(cases)
+
+
 def model_track_all(descs, res, seg):
     st = sx.empty_state(int(seg["base_offset"]), bool(seg["with_offset"]))
     status, tracked = sx.track(st, descs, res, seg)
     return st, status, tracked
 
 
-@pytest.mark.parametrize("name", list(oracle_cases()))
-def test_model_track_equals_the_oracle(name):
-    _, descs, res, segs = oracle_cases()[name]
+def assert_model_equals_oracle(descs, res, segs, entry_cap=None):
+    """The model's track from an empty state against orc.segment_index, field for field; the status."""
     ost, oe = orc.segment_index(descs, res, segs)
-    st, status, tracked = model_track_all(descs, res, segs[0])
+    st = sx.empty_state(int(segs[0]["base_offset"]), bool(segs[0]["with_offset"]))
+    status, tracked = sx.track(st, descs, res, segs[0], entry_cap=entry_cap)
     o = ost[0]
     assert (status, tracked, st.n) == (int(o["status"]), int(o["tracked"]), int(o["entries"]))
     assert (int(st.monotonic), int(st.non_data_timestamps), st.max_offset, st.base_timestamp, st.max_timestamp,
@@ -125,6 +149,26 @@ def test_model_track_equals_the_oracle(name):
     assert st.rel_offset == [int(x) for x in oe["relative_offset"][:st.n]]
     assert st.rel_time == [int(x) for x in oe["relative_time"][:st.n]]
     assert st.position == [int(x) for x in oe["position"][:st.n]]
+    return status
+
+
+@pytest.mark.parametrize("name", list(oracle_cases()))
+def test_model_track_equals_the_oracle(name):
+    _, descs, res, segs = oracle_cases()[name]
+    assert_model_equals_oracle(descs, res, segs)
+
+
+def test_recovery_index_meets_neither_extra_verdict():
+    """The recovery index (segment_index_kernel, rpgpu_index.hip; orc.segment_index) knows OK and
+    OFFSET_BELOW_BASE only.  It is the shared recurrence started from an empty state with a slot of
+    batch_count entries: from such a start NON_DATA_ASSERT and NO_ROOM are unreachable (non_data_timestamps
+    is set only by the step that writes entry 0 and no non-data batch adds an entry after it; at most one
+    entry per batch), so with that cap the model equals the oracle, which has neither."""
+    seen = set()
+    for _, descs, res, segs in random_cases():
+        seen.add(assert_model_equals_oracle(descs, res, segs, entry_cap=int(segs[0]["batch_count"])))
+    assert sum(1 for c in random_cases() if len(c[1])) >= 50
+    assert seen == {0, sx.V_BELOW_BASE}
 
 
 def split_seg(seg, lo, hi):
@@ -239,7 +283,8 @@ def test_host_program_over_the_sweep(hosts, sweep, tmp_path, san):
 def track_jobs():
     """(State, cap, step, rows) with the model's outcome: the oracle's cases whole,
     the split cases at every k (the second half from the first half's state), a
-    cap that runs out, the hostile state."""
+    cap that runs out, the hostile state, the random segments as the recovery index
+    tracks them (from empty, a slot of batch_count entries)."""
     jobs, want = [], []
 
     def add(st, cap, seg, descs, res):
@@ -259,6 +304,9 @@ def track_jobs():
         hostile = sx.empty_state(100, True)
         hostile.non_data_timestamps = True
         add(hostile, 16, segs[0], descs, res)
+    for _, descs, res, segs in random_cases():
+        add(sx.empty_state(int(segs[0]["base_offset"]), bool(segs[0]["with_offset"])), int(segs[0]["batch_count"]),
+            segs[0], descs, res)
     return jobs, want
 
 
