@@ -1730,6 +1730,118 @@ int32_t rpgpu_segidx_find_device(rpgpu_ctx* ctx, const rpgpu_segidx_state* d_sta
                                  const rpgpu_segidx_query* d_queries, uint32_t nq, rpgpu_segidx_found* d_found,
                                  void* hip_stream);
 
+/* ---- aborted transactions ahead of compaction ------------------------------
+ * storage::internal::tx_reducer (storage/compaction_reducers.cc:322-428,
+ * compaction_reducers.h:150-256), which rebuild_compaction_index
+ * (storage/segment_utils.cc:508-555, called from self_compact_segment
+ * :597-620) puts in front of index_rebuilder_reducer: the data batches of
+ * aborted transactions, the commit and abort markers and the tx_prepare
+ * batches never reach the compaction index, so no offset of theirs is in the
+ * keep list and copy_data_segment_reducer drops them.
+ *
+ * Per scope (one segment, its batches in file order) and per batch b, with
+ * ranges = stm_manager::aborted_tx_ranges(base, stable) in a min-heap on first:
+ *   consume_aborted_txs(b.last_offset()) (:322-328): ongoing[r.pid] = r for
+ *     every range with r.first <= b.last_offset(); r.last is not read;
+ *   transactional control batch (:330-362): parse_control_batch
+ *     (cluster/rm_stm.cc:258-279) vasserts type == raft_data, record_count == 1
+ *     and key version == 0 and reads the control type, the second big-endian
+ *     int16 of the first record's key; tx_abort (0) erases ongoing[pid] and is
+ *     discarded, tx_commit (1) is discarded, any other value is kept;
+ *   transactional raft_data batch (:364-372): discarded iff ongoing holds its
+ *     pid = (producer_id, producer_epoch), header bytes [43, 51) and [51, 53);
+ *   control batch without the transactional bit and not raft_data (:374-391):
+ *     vassert tx_prepare (9) or tx_fence (10); prepare is discarded;
+ *   everything else is delegated (:393-428).
+ * The device form is in DESIGN.md §3 ("aborted transactions"). */
+typedef struct rpgpu_tx_range { /* model::tx_range */
+    int64_t producer_id;
+    int16_t producer_epoch;
+    uint16_t reserved0;
+    uint32_t reserved1;
+    int64_t first;
+    int64_t last;
+} rpgpu_tx_range;               /* 32 bytes */
+
+/* rpgpu_tx_scope.flags */
+#define RPGPU_TX_NON_TRANSACTIONAL 1u /* !has_tx_stm(): every batch is delegated (compaction_reducers.cc:394-396) */
+#define RPGPU_TX_FILTER_RANGES 2u     /* only ranges with last >= from && first <= to take part
+                                         (filter_intersecting, cluster/rm_stm.cc:1948-1962): a caller passes a
+                                         partition's aborted list once for all its segments */
+typedef struct rpgpu_tx_scope {
+    uint32_t first_batch, batch_count; /* its descriptors, in file order; scopes are disjoint      */
+    uint32_t range_first, range_count; /* rows of d_ranges; several scopes may name the same rows  */
+    int64_t from, to;                  /* RPGPU_TX_FILTER_RANGES                                   */
+    uint32_t flags;
+    uint32_t reserved;
+} rpgpu_tx_scope;                      /* 40 bytes */
+
+/* d_discard[b] */
+enum rpgpu_tx_discard {
+    RPGPU_TX_DELEGATED = 0,
+    RPGPU_TX_ABORTED_DATA = 1,
+    RPGPU_TX_MARKER = 2,      /* tx_commit or tx_abort                       */
+    RPGPU_TX_PREPARE = 3,
+    RPGPU_TX_NOT_REACHED = 4, /* behind the scope's stop, or in no scope     */
+};
+
+enum rpgpu_tx_status {
+    RPGPU_TX_OK = 0,
+    RPGPU_TX_BAD_BATCH = 1,       /* a verdict other than RPGPU_V_OK: the scope stops there, as a
+                                     segment of rpgpu_segment_index_device does                    */
+    RPGPU_TX_ASSERT = 2,          /* one of the vasserts above: the reference aborts               */
+    RPGPU_TX_KEY_SHORT_THROW = 3, /* the control key is null or shorter than the int16 it is asked
+                                     for: decoder::read_int16 -> iobuf_parser::consume_be_type ->
+                                     io_iterator_consumer::consume_type throws std::out_of_range
+                                     (bytes/details/io_iterator_consumer.h:88-97), which ends the
+                                     consume ("Error rebuilding index", segment_utils.cc:528-533).
+                                     A key of 2 or 3 bytes whose version is not 0 is the vassert. */
+    RPGPU_TX_NOT_INDEXED = 4,     /* a control batch without its index entry                       */
+    RPGPU_TX_BAD_SCOPE = 5,       /* rows outside the arrays: no flag of the scope is written      */
+};
+
+typedef struct rpgpu_tx_stats { /* tx_reducer::stats (compaction_reducers.h:201-224) */
+    uint64_t tx_data_batches_discarded;
+    uint64_t tx_control_batches_discarded;
+    uint64_t non_tx_control_batches_discarded;
+    uint64_t all_batches_discarded;
+    uint64_t num_aborted_txes; /* after RPGPU_TX_FILTER_RANGES                    */
+    uint64_t all_batches;      /* 0 under RPGPU_TX_NON_TRANSACTIONAL              */
+    uint32_t processed;        /* batches in front of the stop                    */
+    int32_t status;            /* enum rpgpu_tx_status                            */
+    uint32_t bad_batch;        /* the batch that stopped the scope (index into d_descs), else UINT32_MAX */
+    uint32_t reserved;
+} rpgpu_tx_stats;              /* 64 bytes */
+
+/* Input: a validated and indexed arena, as rpgpu_compaction_keep_device takes.
+ * d_discard[n]: enum rpgpu_tx_discard per batch.  d_stats[nscopes].  Whether a
+ * batch stops its scope depends on that batch alone; flags and counters are
+ * those of the batches in front of it, the offender and everything behind it
+ * get RPGPU_TX_NOT_REACHED.  Under RPGPU_TX_NON_TRANSACTIONAL only a verdict
+ * stops the scope.  Every output byte is a function of the input.
+ * d_scratch: rpgpu_compaction_tx_scratch_bytes(n, nranges) bytes. */
+size_t rpgpu_compaction_tx_scratch_bytes(uint32_t n, uint32_t nranges);
+int32_t rpgpu_compaction_tx_filter_device(rpgpu_ctx* ctx, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                          const rpgpu_batch_result* d_results, uint32_t n,
+                                          const rpgpu_record_index* d_index, uint64_t index_cap,
+                                          const rpgpu_tx_scope* d_scopes, uint32_t nscopes,
+                                          const rpgpu_tx_range* d_ranges, uint32_t nranges, uint8_t* d_discard,
+                                          rpgpu_tx_stats* d_stats, void* d_scratch, void* hip_stream);
+
+/* rpgpu_compaction_keep_device behind the filter.  d_discard: the filter's
+ * flags, or NULL for none.  The records of a batch flagged 1..3 are not
+ * inserted into the key table (index_rebuilder_reducer never sees them); their
+ * own flag is still "is (scope, offset) in the keep set", because
+ * copy_data_segment_reducer decides by offset alone
+ * (compaction_reducers.h:130-133): 0 in a well-formed segment, so the rewrite
+ * reports RPGPU_COMPACT_DROPPED, and 1 for a hostile duplicate of a kept offset,
+ * exactly as the reference keeps it. */
+int32_t rpgpu_compaction_keep_tx_device(rpgpu_ctx* ctx, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                        const rpgpu_batch_result* d_results, uint32_t n,
+                                        const rpgpu_record_index* d_index, uint64_t index_cap,
+                                        const uint8_t* d_discard, uint8_t* d_keep, uint64_t* d_nkeys,
+                                        void* d_scratch, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,20 @@ SEGIDX_FOUND_DTYPE = np.dtype([("status", "<i4"), ("ix", "<u4"), ("offset", "<i8
 assert SEGIDX_STATE_DTYPE.itemsize == 80 and SEGIDX_TRACKED_DTYPE.itemsize == 16 and SEGIDX_BLOB_DTYPE.itemsize == 32
 assert SEGIDX_FILE_DTYPE.itemsize == 16 and SEGIDX_HYDRATED_DTYPE.itemsize == 16
 assert SEGIDX_QUERY_DTYPE.itemsize == 16 and SEGIDX_FOUND_DTYPE.itemsize == 32
+# aborted transactions ahead of compaction (rpgpu_compaction_tx_filter_device)
+TX_NON_TRANSACTIONAL, TX_FILTER_RANGES = 1, 2  # rpgpu_tx_scope.flags
+TX_DELEGATED, TX_ABORTED_DATA, TX_MARKER, TX_PREPARE, TX_NOT_REACHED = range(5)  # enum rpgpu_tx_discard
+(TX_OK, TX_BAD_BATCH, TX_ASSERT, TX_KEY_SHORT_THROW, TX_NOT_INDEXED, TX_BAD_SCOPE) = range(6)  # enum rpgpu_tx_status
+TX_RANGE_DTYPE = np.dtype([("producer_id", "<i8"), ("producer_epoch", "<i2"), ("reserved0", "<u2"),
+                           ("reserved1", "<u4"), ("first", "<i8"), ("last", "<i8")])
+TX_SCOPE_DTYPE = np.dtype([("first_batch", "<u4"), ("batch_count", "<u4"), ("range_first", "<u4"),
+                           ("range_count", "<u4"), ("from", "<i8"), ("to", "<i8"), ("flags", "<u4"),
+                           ("reserved", "<u4")])
+TX_STATS_DTYPE = np.dtype([("tx_data_batches_discarded", "<u8"), ("tx_control_batches_discarded", "<u8"),
+                           ("non_tx_control_batches_discarded", "<u8"), ("all_batches_discarded", "<u8"),
+                           ("num_aborted_txes", "<u8"), ("all_batches", "<u8"), ("processed", "<u4"),
+                           ("status", "<i4"), ("bad_batch", "<u4"), ("reserved", "<u4")])
+assert TX_RANGE_DTYPE.itemsize == 32 and TX_SCOPE_DTYPE.itemsize == 40 and TX_STATS_DTYPE.itemsize == 64
 INDEX_ENTRY_DTYPE = np.dtype([("relative_offset", "<u4"), ("relative_time", "<u4"), ("position", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 32 and SEGMENT_STATE_DTYPE.itemsize == 48 and INDEX_ENTRY_DTYPE.itemsize == 16
 assert INDEX_DTYPE.itemsize == 32 and RP_HEADER_DTYPE.itemsize == 61
@@ -386,6 +400,10 @@ def lib() -> C.CDLL:
         _sig(L.rpgpu_segidx_write_run_device, _i32, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp)
         _sig(L.rpgpu_segidx_hydrate_device, _i32, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _u64, _vp, _vp)
         _sig(L.rpgpu_segidx_find_device, _i32, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp)
+        _sig(L.rpgpu_compaction_tx_scratch_bytes, C.c_size_t, _u32, _u32)
+        _sig(L.rpgpu_compaction_tx_filter_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32,
+             _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_compaction_keep_tx_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
         _LIB = L
     return _LIB
 
@@ -429,4 +447,5 @@ EXPORTED = [
     "rpgpu_rsindex_find_device",
     "rpgpu_segidx_track_device", "rpgpu_segidx_write_plan_device", "rpgpu_segidx_write_run_device",
     "rpgpu_segidx_hydrate_device", "rpgpu_segidx_find_device",
+    "rpgpu_compaction_tx_scratch_bytes", "rpgpu_compaction_tx_filter_device", "rpgpu_compaction_keep_tx_device",
 ]

@@ -353,17 +353,46 @@ int32_t rpgpu_compaction_rewrite_run_device(rpgpu_ctx* c, const uint8_t* d_data,
     return RPGPU_OK;
 }
 
-int32_t rpgpu_compaction_keep_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
-                                     const rpgpu_batch_result* d_results, uint32_t n,
-                                     const rpgpu_record_index* d_index, uint64_t index_cap, uint8_t* d_keep,
-                                     uint64_t* d_nkeys, void* d_scratch, void* hip_stream) {
+int32_t rpgpu_compaction_keep_tx_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                        const rpgpu_batch_result* d_results, uint32_t n,
+                                        const rpgpu_record_index* d_index, uint64_t index_cap,
+                                        const uint8_t* d_discard, uint8_t* d_keep, uint64_t* d_nkeys,
+                                        void* d_scratch, void* hip_stream) {
     if (!c || !d_nkeys || (n && (!d_data || !d_descs || !d_results)) ||
         (index_cap && (!d_index || !d_keep || !d_scratch)) || index_cap > 0xffffffffull)
         return RPGPU_EINVAL;
     hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    hipError_t e = rpgpu::launch_compaction_keep(d_data, d_descs, d_results, n, d_index, index_cap, d_keep, d_nkeys,
-                                                 d_scratch, s);
+    hipError_t e = rpgpu::launch_compaction_keep(d_data, d_descs, d_results, n, d_index, index_cap, d_discard, d_keep,
+                                                 d_nkeys, d_scratch, s);
     if (e != hipSuccess) return fail(c, e, "compaction launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_compaction_keep_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                     const rpgpu_batch_result* d_results, uint32_t n,
+                                     const rpgpu_record_index* d_index, uint64_t index_cap, uint8_t* d_keep,
+                                     uint64_t* d_nkeys, void* d_scratch, void* hip_stream) {
+    return rpgpu_compaction_keep_tx_device(c, d_data, d_descs, d_results, n, d_index, index_cap, nullptr, d_keep,
+                                           d_nkeys, d_scratch, hip_stream);
+}
+
+size_t rpgpu_compaction_tx_scratch_bytes(uint32_t n, uint32_t nranges) {
+    return rpgpu::compaction_tx_scratch_bytes(n, nranges);
+}
+
+int32_t rpgpu_compaction_tx_filter_device(rpgpu_ctx* c, const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
+                                          const rpgpu_batch_result* d_results, uint32_t n,
+                                          const rpgpu_record_index* d_index, uint64_t index_cap,
+                                          const rpgpu_tx_scope* d_scopes, uint32_t nscopes,
+                                          const rpgpu_tx_range* d_ranges, uint32_t nranges, uint8_t* d_discard,
+                                          rpgpu_tx_stats* d_stats, void* d_scratch, void* hip_stream) {
+    if (!c || (n && (!d_data || !d_descs || !d_results || !d_discard)) || (index_cap && !d_index) ||
+        (nscopes && (!d_scopes || !d_stats || !d_scratch)) || (nranges && !d_ranges) || n > 0x3fffffffu)
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_tx_filter(d_data, d_descs, d_results, n, d_index, index_cap, d_scopes, nscopes,
+                                           d_ranges, nranges, d_discard, d_stats, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "tx filter launch");
     return RPGPU_OK;
 }
 

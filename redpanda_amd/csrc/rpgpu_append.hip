@@ -10,15 +10,10 @@
 //   append_classify_kernel  one lane per batch: the sort key (the log, or the
 //                           sentinel nlogs for a batch that is not appended)
 //                           and the per-log batch counts
-//   append_hist_kernel /    a stable LSD radix sort of the batch indices on
-//   append_scatter_kernel   the key, 8-bit digits, ceil(log2(nlogs + 1) / 8)
-//                           passes.  Per pass: a digit histogram per block of
-//                           1024 batches, an exclusive scan of the digits x
-//                           blocks table (digit-major), a stable scatter.
-//                           The rank inside a wave is a ballot match
-//                           (popc(same-digit lanes below)), the waves of a
-//                           block are combined in LDS in wave order: no
-//                           atomic ticket, the order is the descriptors'.
+//   radix_sort_items        (rpgpu_sort.h) a stable LSD radix sort of the batch
+//                           indices on the key, 8-bit digits,
+//                           ceil(log2(nlogs + 1) / 8) passes; no atomic
+//                           ticket, the order is the descriptors'.
 //   append_walk_kernel      one wavefront per log, 64 batches per step: wave
 //                           scans of lod + 1 and of size_bytes carry the next
 //                           offset, the file position and the bytes left
@@ -47,12 +42,11 @@
 #include "rpgpu_device.h"
 #include "rpgpu_launch.h"
 #include "rpgpu_scan.h"
+#include "rpgpu_sort.h"
 
 namespace rpgpu {
 namespace {
 
-constexpr uint32_t kSortBlock = 1024;  // batches per sort block (16 waves, one batch per lane)
-constexpr uint32_t kSortWaves = kSortBlock / 64;
 constexpr uint32_t kScanThreads = 1024;
 constexpr uint8_t kGhostBatch = 7;  // model::record_batch_type::ghost_batch
 static_assert(sizeof(rpgpu_append_log) == 32 && sizeof(rpgpu_append_batch) == 32 &&
@@ -65,7 +59,6 @@ struct ApParts {
     rpgpu_append_segment* segs;
 };
 size_t ap_al(size_t x) { return (x + 255) & ~(size_t)255; }
-uint32_t sort_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + kSortBlock - 1) / kSortBlock); }
 size_t ap_layout(void* p, uint32_t n, uint32_t nlogs, ApParts* out) {
     uint8_t* b = static_cast<uint8_t*>(p);
     size_t o = 0;
@@ -80,13 +73,6 @@ size_t ap_layout(void* p, uint32_t n, uint32_t nlogs, ApParts* out) {
     if (out) *out = s;
     return o;
 }
-// digits of the largest key, the sentinel nlogs
-uint32_t sort_passes(uint32_t nlogs) {
-    uint32_t bits = 1;
-    while (bits < 32 && (nlogs >> bits)) bits++;
-    return (bits + 7) / 8;
-}
-
 __global__ __launch_bounds__(256) void append_classify_kernel(const rpgpu_batch_desc* __restrict__ descs,
                                                               const rpgpu_batch_result* __restrict__ res, uint32_t n,
                                                               const int32_t* __restrict__ codes,
@@ -116,67 +102,6 @@ __global__ __launch_bounds__(256) void append_classify_kernel(const rpgpu_batch_
         b.segment = 0;
         b.reserved = 0;
         rows[i] = b;
-    }
-}
-
-// in-place exclusive scan of a[0, len) by one workgroup
-__global__ __launch_bounds__(kScanBlock) void append_scan_kernel(uint32_t* a, uint32_t len) {
-    __shared__ uint32_t part[kScanBlock];
-    (void)array_scan_excl(a, a, len, part);
-}
-
-// item i of a pass's input order (pass 0: the descriptors' own order)
-__device__ __forceinline__ uint32_t sort_item(const uint32_t* __restrict__ in, uint32_t i) { return in ? in[i] : i; }
-
-__global__ __launch_bounds__(kSortBlock) void append_hist_kernel(const uint32_t* __restrict__ key,
-                                                                 const uint32_t* __restrict__ in, uint32_t n,
-                                                                 uint32_t shift, uint32_t nblocks,
-                                                                 uint32_t* __restrict__ table) {
-    __shared__ uint32_t h[256];
-    if (threadIdx.x < 256) h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * kSortBlock + threadIdx.x;
-    if (i < n) atomicAdd(&h[(key[sort_item(in, (uint32_t)i)] >> shift) & 255u], 1u);
-    __syncthreads();
-    if (threadIdx.x < 256) table[(size_t)threadIdx.x * nblocks + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(kSortBlock) void append_scatter_kernel(const uint32_t* __restrict__ key,
-                                                                    const uint32_t* __restrict__ in, uint32_t n,
-                                                                    uint32_t shift, uint32_t nblocks,
-                                                                    const uint32_t* __restrict__ table,
-                                                                    uint32_t* __restrict__ out) {
-    __shared__ uint32_t wc[kSortWaves][256];  // per wave and digit: count, then the count of the waves before
-    for (uint32_t q = threadIdx.x; q < kSortWaves * 256; q += kSortBlock) (&wc[0][0])[q] = 0;
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * kSortBlock + threadIdx.x;
-    const bool live = i < n;
-    const uint32_t item = live ? sort_item(in, (uint32_t)i) : 0u;
-    const uint32_t dg = live ? (key[item] >> shift) & 255u : 0u;
-    // lanes of this wave with the same digit
-    uint64_t m = __ballot(live);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const bool bit = (dg >> b) & 1u;
-        const uint64_t bb = __ballot(bit);
-        m &= bit ? bb : ~bb;
-    }
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint64_t below = m & ((1ull << lane) - 1);
-    if (live && below == 0) wc[w][dg] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x < 256) {
-        uint32_t run = 0;
-        for (uint32_t k = 0; k < kSortWaves; k++) {
-            const uint32_t v = wc[k][threadIdx.x];
-            wc[k][threadIdx.x] = run;
-            run += v;
-        }
-    }
-    __syncthreads();
-    if (live) {
-        const uint64_t at = (uint64_t)table[(size_t)dg * nblocks + blockIdx.x] + wc[w][dg] + (uint32_t)__popcll(below);
-        if (at < n) out[at] = item;
     }
 }
 
@@ -517,20 +442,10 @@ hipError_t launch_append_plan(const rpgpu_batch_desc* d_descs, const rpgpu_batch
         RPGPU_LAUNCH_CHECK();
     }
     if (nlogs == 0) return hipSuccess;
-    append_scan_kernel<<<1, kScanBlock, 0, s>>>(p.starts, nlogs + 1);
+    radix_scan_kernel<<<1, kScanBlock, 0, s>>>(p.starts, nlogs + 1);
     RPGPU_LAUNCH_CHECK();
-    const uint32_t passes = sort_passes(nlogs), nb = sort_blocks(n);
-    const uint32_t* in = nullptr;
-    for (uint32_t k = 0; n && k < passes; k++) {
-        uint32_t* out = (k & 1) ? p.idx_b : p.idx_a;
-        append_hist_kernel<<<nb, kSortBlock, 0, s>>>(p.key, in, n, 8 * k, nb, p.table);
-        RPGPU_LAUNCH_CHECK();
-        append_scan_kernel<<<1, kScanBlock, 0, s>>>(p.table, nb * 256);
-        RPGPU_LAUNCH_CHECK();
-        append_scatter_kernel<<<nb, kSortBlock, 0, s>>>(p.key, in, n, 8 * k, nb, p.table, out);
-        RPGPU_LAUNCH_CHECK();
-        in = out;
-    }
+    const uint32_t* in = nullptr;  // the largest key is the sentinel nlogs
+    if ((e = radix_sort_items(p.key, n, nlogs, p.idx_a, p.idx_b, p.table, &in, s)) != hipSuccess) return e;
     append_walk_kernel<<<wave_grid(nlogs), 256, 0, s>>>(d_descs, d_res, d_logs, nlogs, in, p.starts, d_rows, p.dst,
                                                         p.segs, d_lres);
     RPGPU_LAUNCH_CHECK();

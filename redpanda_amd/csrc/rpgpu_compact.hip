@@ -24,6 +24,8 @@
 //   compact_set_kernel    one lane per table slot: each key's latest offset
 //                         into the keep set (slot ids, hashed by scope+offset)
 //   compact_keep_kernel   one lane per record: keep = (scope, offset) in the set
+// rpgpu_compaction_keep_tx_device: the records of a batch the tx filter flagged
+// take no part in the key table; their own flag is still the set lookup.
 // Everything is a CAS or a max on 32/64-bit words of a table twice the record
 // count; no ordering between lanes matters (the latest offset per key is a
 // max, the set a union), so the result is independent of scheduling.
@@ -42,7 +44,7 @@ struct CompactRec {  // 32 B per index entry
     uint64_t key_abs;  // arena offset of the key bytes
     uint32_t key_len;  // 0 for null and empty keys
     uint32_t scope;    // desc.partition
-    uint8_t state;     // 0 none, 1 indexed
+    uint8_t state;     // 0 none, 1 indexed, 2 withheld from the index (the tx filter), looked up only
     uint8_t type;
     uint8_t pad[6];
 };
@@ -119,8 +121,9 @@ __global__ __launch_bounds__(256) void compact_keys_kernel(const uint8_t* __rest
                                                            const rpgpu_batch_desc* __restrict__ descs,
                                                            const rpgpu_batch_result* __restrict__ res, uint32_t n,
                                                            const rpgpu_record_index* __restrict__ index,
-                                                           uint64_t index_cap, uint8_t* __restrict__ keep,
-                                                           CompactRec* __restrict__ rec) {
+                                                           uint64_t index_cap,
+                                                           const uint8_t* __restrict__ discard,
+                                                           uint8_t* __restrict__ keep, CompactRec* __restrict__ rec) {
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t waves = (gridDim.x * blockDim.x) >> 6;
     const uint32_t lid = lane_id();
@@ -133,6 +136,9 @@ __global__ __launch_bounds__(256) void compact_keys_kernel(const uint8_t* __rest
         const uint8_t type = r.type;
         const bool comp = compactible(type);
         const rpgpu_batch_desc d = descs[b];
+        // tx_reducer never hands the batch to index_rebuilder_reducer (rpgpu_compaction_tx_filter_device)
+        const uint8_t dis = discard ? discard[b] : (uint8_t)RPGPU_TX_DELEGATED;
+        const uint8_t state = dis >= RPGPU_TX_ABORTED_DATA && dis <= RPGPU_TX_PREPARE ? 2 : 1;
         for (uint64_t j = first + lid; j < end; j += 64) {
             if (!comp) {
                 keep[j] = 1;  // copied whole (compaction_reducers.cc:117-123)
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void compact_keys_kernel(const uint8_t* __rest
             c.key_len = e.key_len > 0 ? (uint32_t)e.key_len : 0u;
             c.scope = d.partition;
             c.type = type;
-            c.state = 1;
+            c.state = state;
             c.hash = key_hash(data + c.key_abs, c.key_len, c.scope, type);
             rec[j] = c;
         }
@@ -208,7 +214,7 @@ __global__ __launch_bounds__(256) void compact_keep_kernel(const rpgpu_record_in
     const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= index_cap) return;
     const CompactRec me = rec[j];
-    if (me.state != 1) return;
+    if (me.state == 0) return;
     const int64_t o = index[j].offset;
     const uint64_t mask = cap - 1;
     uint64_t pos = set_hash(me.scope, o) & mask;
@@ -226,8 +232,8 @@ __global__ __launch_bounds__(256) void compact_keep_kernel(const rpgpu_record_in
 
 hipError_t launch_compaction_keep(const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
                                   const rpgpu_batch_result* d_res, uint32_t n, const rpgpu_record_index* d_index,
-                                  uint64_t index_cap, uint8_t* d_keep, uint64_t* d_nkeys, void* d_scratch,
-                                  hipStream_t s) {
+                                  uint64_t index_cap, const uint8_t* d_discard, uint8_t* d_keep, uint64_t* d_nkeys,
+                                  void* d_scratch, hipStream_t s) {
     hipError_t e = hipMemsetAsync(d_nkeys, 0, sizeof(uint64_t), s);
     if (e != hipSuccess || index_cap == 0) return e;
     if ((e = hipMemsetAsync(d_keep, 2, index_cap, s)) != hipSuccess) return e;
@@ -235,7 +241,8 @@ hipError_t launch_compaction_keep(const uint8_t* d_data, const rpgpu_batch_desc*
     const CompactParts p = compact_parts(d_scratch, index_cap);
     if (n) {
         const uint32_t blocks = (uint32_t)(((uint64_t)n * 64 + 255) / 256 < 65536 ? ((uint64_t)n * 64 + 255) / 256 : 65536);
-        compact_keys_kernel<<<blocks, 256, 0, s>>>(d_data, d_descs, d_res, n, d_index, index_cap, d_keep, p.rec);
+        compact_keys_kernel<<<blocks, 256, 0, s>>>(d_data, d_descs, d_res, n, d_index, index_cap, d_discard, d_keep,
+                                                   p.rec);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const uint32_t rb = (uint32_t)((index_cap + 255) / 256);

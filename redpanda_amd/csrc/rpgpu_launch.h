@@ -105,8 +105,8 @@ hipError_t launch_compress_run(const rpgpu_batch_desc* d_descs, uint32_t n, cons
 size_t compaction_scratch_bytes(uint64_t index_cap);
 hipError_t launch_compaction_keep(const uint8_t* d_data, const rpgpu_batch_desc* d_descs,
                                   const rpgpu_batch_result* d_res, uint32_t n, const rpgpu_record_index* d_index,
-                                  uint64_t index_cap, uint8_t* d_keep, uint64_t* d_nkeys, void* d_scratch,
-                                  hipStream_t s);
+                                  uint64_t index_cap, const uint8_t* d_discard, uint8_t* d_keep, uint64_t* d_nkeys,
+                                  void* d_scratch, hipStream_t s);
 hipError_t launch_timequery(const rpgpu_batch_result* d_res, uint32_t n, const rpgpu_record_index* d_index,
                             const rpgpu_timequery* d_q, uint32_t nq, rpgpu_timequery_result* d_out, hipStream_t s);
 size_t compaction_rewrite_scratch_bytes(uint32_t n);
@@ -184,6 +184,14 @@ hipError_t launch_segidx_hydrate(const uint8_t* d_files, uint64_t files_bytes, c
 hipError_t launch_segidx_find(const rpgpu_segidx_state* d_states, uint32_t nstates, const rpgpu_index_entry* d_entries,
                               uint64_t nentries, const rpgpu_segidx_query* d_queries, uint32_t nq,
                               rpgpu_segidx_found* d_found, hipStream_t s);
+
+// ---- rpgpu_txfilter.hip
+size_t compaction_tx_scratch_bytes(uint32_t n, uint32_t nranges);
+hipError_t launch_tx_filter(const uint8_t* d_data, const rpgpu_batch_desc* d_descs, const rpgpu_batch_result* d_res,
+                            uint32_t n, const rpgpu_record_index* d_index, uint64_t index_cap,
+                            const rpgpu_tx_scope* d_scopes, uint32_t nscopes, const rpgpu_tx_range* d_ranges,
+                            uint32_t nranges, uint8_t* d_discard, rpgpu_tx_stats* d_stats, void* d_scratch,
+                            hipStream_t s);
 
 }  // namespace rpgpu
 #endif

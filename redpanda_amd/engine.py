@@ -571,6 +571,77 @@ class Engine:
         torch.cuda.synchronize(dev)
         return d_keep.cpu().numpy()[:cap].copy(), int(d_nkeys.item())
 
+    def compaction_keep_tx(self, data: np.ndarray, descs: np.ndarray, results: np.ndarray, index: np.ndarray,
+                           discard: np.ndarray | None) -> tuple[np.ndarray, int]:
+        """rpgpu_compaction_keep_tx_device: compaction_keep behind the tx filter.
+        discard: tx_filter's flags per batch, or None for a null pointer."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        n, cap = len(descs), len(index)
+
+        def up(a, dtype):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(dev)
+
+        d_data = up(np.concatenate([np.asarray(data, np.uint8), np.zeros(abi.ARENA_TAIL_PAD, np.uint8)]), np.uint8)
+        d_descs, d_res, d_idx = up(descs, abi.DESC_DTYPE), up(results, abi.RESULT_DTYPE), up(index, abi.INDEX_DTYPE)
+        d_dis = None
+        if discard is not None:
+            if len(discard) != n:
+                raise ValueError("one discard flag per batch")
+            d_dis = up(np.concatenate([np.asarray(discard, np.uint8), np.zeros(1, np.uint8)]), np.uint8)
+        d_keep = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        d_nkeys = torch.empty(1, dtype=torch.int64, device=dev)
+        d_scr = torch.empty(max(int(self._lib.rpgpu_compaction_scratch_bytes(cap)), 1), dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_compaction_keep_tx_device(self._ctx, d_data.data_ptr(), d_descs.data_ptr(),
+                                                       d_res.data_ptr(), n, d_idx.data_ptr(), cap,
+                                                       d_dis.data_ptr() if d_dis is not None else None,
+                                                       d_keep.data_ptr(), d_nkeys.data_ptr(), d_scr.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_compaction_keep_tx_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        return d_keep.cpu().numpy()[:cap].copy(), int(d_nkeys.item())
+
+    def tx_filter(self, data: np.ndarray, descs: np.ndarray, results: np.ndarray, index: np.ndarray,
+                  scopes: np.ndarray, ranges: np.ndarray, guard: int = 64) -> dict:
+        """rpgpu_compaction_tx_filter_device over a validated + indexed arena
+        (host copies in, host copies out): discard (one flag per batch) and
+        stats (one row per scope).  Both device outputs are pre-filled with
+        0xA5 and carry `guard` more bytes / one more row behind them; the
+        whole buffers come back as discard_raw and stats_raw."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        scopes = np.ascontiguousarray(scopes, dtype=abi.TX_SCOPE_DTYPE)
+        ranges = np.ascontiguousarray(ranges, dtype=abi.TX_RANGE_DTYPE)
+        n, cap, ns, nr = len(descs), len(index), len(scopes), len(ranges)
+
+        def up(a, dtype, pad):
+            a = np.ascontiguousarray(a, dtype=dtype).view(np.uint8).reshape(-1)
+            return torch.from_numpy(np.concatenate([a, np.zeros(pad, np.uint8)])).to(dev)
+
+        d_data = up(data, np.uint8, abi.ARENA_TAIL_PAD)
+        d_descs, d_res, d_idx = up(descs, abi.DESC_DTYPE, 24), up(results, abi.RESULT_DTYPE, 64), up(index, abi.INDEX_DTYPE, 32)
+        d_scopes, d_ranges = up(scopes, abi.TX_SCOPE_DTYPE, 40), up(ranges, abi.TX_RANGE_DTYPE, 32)
+        row = abi.TX_STATS_DTYPE.itemsize
+        d_dis = torch.full((n + guard,), 0xA5, dtype=torch.uint8, device=dev)
+        d_stats = torch.full(((ns + 1) * row,), 0xA5, dtype=torch.uint8, device=dev)
+        d_scr = torch.empty(max(int(self._lib.rpgpu_compaction_tx_scratch_bytes(n, nr)), 1), dtype=torch.uint8,
+                            device=dev)
+        rc = self._lib.rpgpu_compaction_tx_filter_device(self._ctx, d_data.data_ptr(), d_descs.data_ptr(),
+                                                         d_res.data_ptr(), n, d_idx.data_ptr(), cap,
+                                                         d_scopes.data_ptr(), ns, d_ranges.data_ptr(), nr,
+                                                         d_dis.data_ptr(), d_stats.data_ptr(), d_scr.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_compaction_tx_filter_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        dis_raw, stats_raw = d_dis.cpu().numpy(), d_stats.cpu().numpy()
+        return dict(discard=dis_raw[:n].copy(), stats=stats_raw[:ns * row].view(abi.TX_STATS_DTYPE).copy(),
+                    discard_raw=dis_raw, stats_raw=stats_raw)
+
     def kafka_serialize(self, data: np.ndarray, descs: np.ndarray, terms=None, ranges=None):
         """rpgpu_kafka_serialize_device: on-disk batches -> Kafka wire batches at
         the same offsets, plus per-range serializer summaries.  (out, summaries)."""
