@@ -1842,6 +1842,147 @@ int32_t rpgpu_compaction_keep_tx_device(rpgpu_ctx* ctx, const uint8_t* d_data, c
                                         const uint8_t* d_discard, uint8_t* d_keep, uint64_t* d_nkeys,
                                         void* d_scratch, void* hip_stream);
 
+/* ---- produce batches from records -------------------------------------------
+ * Replaces kafka::client::client::produce_records (kafka/client/client.cc:231-271),
+ * which is behind the REST proxy's POST /topics/{topic}
+ * (pandaproxy/rest/handlers.cc:198-199): a partition per record
+ * (kafka/client/partitioners.cc:25-109), one storage::record_batch_builder per
+ * partition, add_raw_kw, build() (storage/record_batch_builder.cc:29-102).
+ * The JSON parse and the base64 decode stay on the host: the
+ * engine takes decoded rows.
+ *
+ * A call holds many independent requests; one request is one produce_records
+ * call (one topic, one partitioner state) and owns the next `nrows` rows, the
+ * record_essences in request order.  The partition of a row is
+ * default_partitioner, the first rule that answers:
+ *  1. RPGPU_PRODUCE_HAS_PARTITION: the row's id as it is (identity_partitioner
+ *     checks nothing: a negative id or one >= partition_count gets a batch of
+ *     its own; the broker rejects it later);
+ *  2. a key that is present and not empty: murmur2(key, len, 0x9747b28c) %
+ *     partition_count (hashing/murmur.cc:384-432, hashing/murmur.h:38-44):
+ *     4-byte little-endian words, a tail of 3 / 2 / 1 bytes with fall-through,
+ *     the modulus on the unsigned hash (Java clients mask the sign bit first;
+ *     the reference does not, and neither does the engine);
+ *  3. otherwise (rr_initial + k) % partition_count, k = the earlier rows of the
+ *     request that reached this rule (roundrobin_partitioner, _next++).
+ * rr_next = rr_initial + the rows that reached rule 3; the caller carries it
+ * to the topic's next request.  partition_count 0 stands for a topic that is
+ * not in the client's cache: partition_for throws topic_error and
+ * produce_records assigns partition 0 (client.cc:240-246), so every row without
+ * its own id goes to partition 0 and the counter does not advance.
+ *
+ * Rows of one request with the same partition form one batch, in request order
+ * (offset delta = rank in the group).  The reference emits a request's
+ * partitions in absl::node_hash_map iteration order, which is no function of
+ * the input; the engine's order is ascending request, then ascending partition
+ * id as a signed int32 (unpinned).
+ *
+ * The batch is record_batch_builder::build() with nothing set: on-disk layout,
+ * size_bytes 61 + body, base_offset 0, type raft_data (1), attrs 0,
+ * last_offset_delta n - 1, record_count n, first_timestamp = max_timestamp =
+ * the request's now_ms (the caller's model::timestamp::now()), producer id /
+ * epoch / base sequence -1, crc = crc_record_batch, header_crc =
+ * internal_header_only_crc.  Record d is vint(len) 00 00 vint(d) vint(klen)
+ * key vint(vlen | -1) value 00.  produce_records passes key.value_or(iobuf{})
+ * (client.cc:257-260): an absent key is encoded as length 0, never -1; a null
+ * value is -1.  Headers are always empty on this path (the proxy's handler
+ * never sets them): the row format has none.
+ *
+ * Hand vectors.  murmur2: "21" c5f2f8ec, "foobar" d0e47bbe,
+ * "a-little-bit-long-string" c53b1da0, "a-little-bit-longer-string" a768c9c3,
+ * "lkjh234lh9fiuh90y23oiuhsafujhadof229phr9h19h89h8" fc7d49cd, "abc" 1c94221b,
+ * "the key" c4c66957 (% 6 = 1), "k" a291e5e0 (% 6 = 4), "" 106e08d9.
+ * One request, partition_count 6, rr_initial 5, rows r0 (id 4, no key, "v0"),
+ * r1 (key "the key", null value), r2 (no key, "hi"), r3 (key of length 0,
+ * value of length 0), r4 (key "k", value "v"): rr_next 7 and four batches,
+ *   partition 0 (r3)      0c 00 00 00 00 00 00
+ *   partition 1 (r1)      1a 00 00 00 0e 74 68 65 20 6b 65 79 01 00
+ *   partition 4 (r0, r4)  10 00 00 00 00 04 76 30 00 10 00 00 02 02 6b 02 76 00
+ *   partition 5 (r2)      10 00 00 00 00 04 68 69 00 */
+#define RPGPU_PRODUCE_HAS_PARTITION 1u
+typedef struct rpgpu_produce_row {
+    uint64_t key_off, val_off; /* into d_data; ignored when the length is <= 0 */
+    int32_t key_len;           /* -1 no key (encoded as an empty one)          */
+    int32_t val_len;           /* -1 null value                                */
+    int32_t partition;         /* used iff flags & RPGPU_PRODUCE_HAS_PARTITION */
+    uint32_t flags;
+} rpgpu_produce_row;           /* 32 bytes */
+typedef struct rpgpu_produce_request { /* requests tile the rows in order */
+    int64_t now_ms;
+    uint32_t nrows;
+    uint32_t partition_count; /* 0: topic not in the cache */
+    int32_t rr_initial;
+    uint32_t pad;
+} rpgpu_produce_request;      /* 24 bytes */
+
+/* The request statuses are the engine's own guard rails (the reference's inputs
+ * are typed, so they are unpinned).  A request keeps the first that applies, in
+ * this order; a request whose status is not OK emits no batch and the other
+ * requests are unaffected. */
+enum rpgpu_produce_status {
+    RPGPU_PRODUCE_OK = 0,
+    RPGPU_PRODUCE_BAD_REQUEST = 1, /* every request of the call: the requests' nrows do not sum to
+                                      nrows.  One request: partition_count > INT32_MAX, rr_initial
+                                      < 0 (both ahead of BAD_ROW), or rr_initial + its rule-3 rows
+                                      pass INT32_MAX (behind BAD_ROW; signed overflow in the
+                                      reference)                                                  */
+    RPGPU_PRODUCE_BAD_ROW = 2,     /* a length below -1, or a key / value range outside data_bytes */
+    RPGPU_PRODUCE_TOO_LARGE = 3,   /* a body that would make size_bytes pass INT32_MAX             */
+    RPGPU_PRODUCE_OUT_OVERFLOW = 4 /* out_cap is too small for the request's batches               */
+};
+typedef struct rpgpu_produce_result { /* per request */
+    int32_t status;
+    int32_t rr_next;      /* OK: rr_initial + the rule-3 rows; else rr_initial                     */
+    uint32_t first_batch; /* OK: the request's batches are rows [first_batch, first_batch + nbatches)
+                             of d_batches; else 0                                                  */
+    uint32_t nbatches;    /* 0 unless OK; a request with zero rows is OK with zero batches         */
+} rpgpu_produce_result;   /* 16 bytes */
+typedef struct rpgpu_produce_batch { /* per emitted batch */
+    uint32_t request;     /* UINT32_MAX in the unused rows */
+    int32_t partition;
+    uint32_t record_count;
+    uint32_t pad;
+    uint64_t out_offset; /* the batch in d_out (64-byte aligned) */
+    uint64_t out_len;    /* 61 + body; 0 in the unused rows      */
+} rpgpu_produce_batch;   /* 32 bytes */
+
+/* The stream and alignment rules of rpgpu_legacy_*: plan, then run with the
+ * same d_scratch, on one stream; a plan may be run any number of times.  Plan:
+ * *d_out_bytes = the output slots of the requests that are OK so far,
+ * *d_nbatches = their batches (<= nrows, so a caller may size the per-batch
+ * arrays by nrows without reading the plan back).  Run: d_out is 16-byte
+ * aligned (RPGPU_EINVAL otherwise) and holds *d_out_bytes +
+ * RPGPU_ARENA_TAIL_PAD bytes; out_cap is the buffer's size, pad included.  A
+ * request whose last slot does not end RPGPU_ARENA_TAIL_PAD bytes in front of
+ * out_cap (the validation reads that far past a batch) gets OUT_OVERFLOW; slots
+ * ascend with the request, so those are the last ones, and nothing is written
+ * past out_cap.  d_req_results[nrequests]; d_batches, d_out_descs and
+ * d_out_results have nrows rows each and all of them are written: the emitted
+ * batches first, in order, then unused rows (out_len 0; descriptor length 0
+ * and ops 0; verdict STREAM_SHORT, as rpgpu_decomp_run_device leaves a batch
+ * it did not rewrite).  d_row_batch[i] / d_row_delta[i]: the row of d_batches
+ * and the offset delta row i received (produce_batcher::handle_response answers
+ * per record), UINT32_MAX for the rows of a refused request.  d_out_descs (ops
+ * CRC | HDRCRC | RECRC | PARSE | INDEX, the descriptor's partition = the batch's
+ * partition id), d_out_results, d_index (capacity needed: nrows) and
+ * *d_index_used are written exactly as rpgpu_legacy_run_device /
+ * rpgpu_decomp_run_device write them, so the output feeds rpgpu_run_device,
+ * rpgpu_kafka_serialize_device, rpgpu_compress_* and rpgpu_append_* unchanged.
+ * nrows and nrequests are at most 2^30 (RPGPU_EINVAL).
+ * d_scratch: rpgpu_produce_scratch_bytes(nrows, nrequests) bytes. */
+size_t rpgpu_produce_scratch_bytes(uint32_t nrows, uint32_t nrequests);
+int32_t rpgpu_produce_plan_device(rpgpu_ctx* ctx, const rpgpu_produce_row* d_rows, uint32_t nrows,
+                                  const rpgpu_produce_request* d_requests, uint32_t nrequests,
+                                  const uint8_t* d_data, uint64_t data_bytes, uint64_t* d_out_bytes,
+                                  uint32_t* d_nbatches, void* d_scratch, void* hip_stream);
+int32_t rpgpu_produce_run_device(rpgpu_ctx* ctx, const rpgpu_produce_row* d_rows, uint32_t nrows,
+                                 const rpgpu_produce_request* d_requests, uint32_t nrequests,
+                                 const uint8_t* d_data, uint64_t data_bytes, rpgpu_produce_result* d_req_results,
+                                 rpgpu_produce_batch* d_batches, uint32_t* d_row_batch, uint32_t* d_row_delta,
+                                 uint8_t* d_out, uint64_t out_cap, rpgpu_batch_desc* d_out_descs,
+                                 rpgpu_batch_result* d_out_results, rpgpu_record_index* d_index,
+                                 uint64_t index_cap, uint64_t* d_index_used, void* d_scratch, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,8 +21,8 @@ ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 LIBRPGPU = PKG / "librpgpu.so"
 LIBRPGEN = PKG / "librpgen.so"
 
-RPGPU_SRCS = ["rpgpu_kernels.hip", "rpgpu_decomp.hip", "rpgpu_sets.hip", "rpgpu_index.hip", "rpgpu_summary.hip", "rpgpu_compact.hip", "rpgpu_compact_rw.hip", "rpgpu_fetch.hip", "rpgpu_compress.hip", "rpgpu_stamp.hip", "rpgpu_legacy.hip", "rpgpu_pp.hip", "rpgpu_append.hip", "rpgpu_rsindex.hip", "rpgpu_segidx.hip", "rpgpu_txfilter.hip", "rpgpu_abi.cpp", "rpgpu_tables.cpp"]
-RPGPU_HDRS = ["rpgpu_internal.h", "rpgpu_launch.h", "rpgpu_device.h", "rpgpu_scan.h", "rpgpu_rewrite.h", "rpgpu_walk.h", "rpgpu_copy.h", "rpgpu_legacy.h", "rpgpu_pp.h", "rpgpu_dfor.h", "rpgpu_segidx.h", "rpgpu_sort.h", "rpgpu_txfilter.h", "rpgpu_codec.h", "rpgpu_zstd.h", "rpgpu_zseq.h", "rpgpu_zblk.h", "rpgpu_wave.h", "rpgpu_inflate.h", "rpgpu_lz4c.h", "rpgpu_snappyc.h", "rpgpu_deflatec.h", "rpgpu_zstdc.h"]
+RPGPU_SRCS = ["rpgpu_kernels.hip", "rpgpu_decomp.hip", "rpgpu_sets.hip", "rpgpu_index.hip", "rpgpu_summary.hip", "rpgpu_compact.hip", "rpgpu_compact_rw.hip", "rpgpu_fetch.hip", "rpgpu_compress.hip", "rpgpu_stamp.hip", "rpgpu_legacy.hip", "rpgpu_pp.hip", "rpgpu_append.hip", "rpgpu_rsindex.hip", "rpgpu_segidx.hip", "rpgpu_txfilter.hip", "rpgpu_produce.hip", "rpgpu_abi.cpp", "rpgpu_tables.cpp"]
+RPGPU_HDRS = ["rpgpu_internal.h", "rpgpu_launch.h", "rpgpu_device.h", "rpgpu_scan.h", "rpgpu_rewrite.h", "rpgpu_walk.h", "rpgpu_copy.h", "rpgpu_legacy.h", "rpgpu_pp.h", "rpgpu_dfor.h", "rpgpu_segidx.h", "rpgpu_sort.h", "rpgpu_txfilter.h", "rpgpu_emit.h", "rpgpu_produce.h", "rpgpu_codec.h", "rpgpu_zstd.h", "rpgpu_zseq.h", "rpgpu_zblk.h", "rpgpu_wave.h", "rpgpu_inflate.h", "rpgpu_lz4c.h", "rpgpu_snappyc.h", "rpgpu_deflatec.h", "rpgpu_zstdc.h"]
 RPGEN_SRCS = ["rpgen.cpp"]
 RPGEN_HDRS = ["rpgen.h"]
 

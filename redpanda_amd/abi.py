@@ -248,6 +248,18 @@ TX_STATS_DTYPE = np.dtype([("tx_data_batches_discarded", "<u8"), ("tx_control_ba
                            ("num_aborted_txes", "<u8"), ("all_batches", "<u8"), ("processed", "<u4"),
                            ("status", "<i4"), ("bad_batch", "<u4"), ("reserved", "<u4")])
 assert TX_RANGE_DTYPE.itemsize == 32 and TX_SCOPE_DTYPE.itemsize == 40 and TX_STATS_DTYPE.itemsize == 64
+# produce batches from records (rpgpu_produce_plan_device / rpgpu_produce_run_device)
+PRODUCE_HAS_PARTITION = 1  # rpgpu_produce_row.flags
+(PRODUCE_OK, PRODUCE_BAD_REQUEST, PRODUCE_BAD_ROW, PRODUCE_TOO_LARGE, PRODUCE_OUT_OVERFLOW) = range(5)  # enum rpgpu_produce_status
+PRODUCE_ROW_DTYPE = np.dtype([("key_off", "<u8"), ("val_off", "<u8"), ("key_len", "<i4"), ("val_len", "<i4"),
+                              ("partition", "<i4"), ("flags", "<u4")])
+PRODUCE_REQUEST_DTYPE = np.dtype([("now_ms", "<i8"), ("nrows", "<u4"), ("partition_count", "<u4"),
+                                  ("rr_initial", "<i4"), ("pad", "<u4")])
+PRODUCE_RESULT_DTYPE = np.dtype([("status", "<i4"), ("rr_next", "<i4"), ("first_batch", "<u4"), ("nbatches", "<u4")])
+PRODUCE_BATCH_DTYPE = np.dtype([("request", "<u4"), ("partition", "<i4"), ("record_count", "<u4"), ("pad", "<u4"),
+                                ("out_offset", "<u8"), ("out_len", "<u8")])
+assert PRODUCE_ROW_DTYPE.itemsize == 32 and PRODUCE_REQUEST_DTYPE.itemsize == 24
+assert PRODUCE_RESULT_DTYPE.itemsize == 16 and PRODUCE_BATCH_DTYPE.itemsize == 32
 INDEX_ENTRY_DTYPE = np.dtype([("relative_offset", "<u4"), ("relative_time", "<u4"), ("position", "<u8")])
 assert SEGMENT_DTYPE.itemsize == 32 and SEGMENT_STATE_DTYPE.itemsize == 48 and INDEX_ENTRY_DTYPE.itemsize == 16
 assert INDEX_DTYPE.itemsize == 32 and RP_HEADER_DTYPE.itemsize == 61
@@ -404,6 +416,10 @@ def lib() -> C.CDLL:
         _sig(L.rpgpu_compaction_tx_filter_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _u32,
              _vp, _vp, _vp, _vp)
         _sig(L.rpgpu_compaction_keep_tx_device, _i32, _vp, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_produce_scratch_bytes, C.c_size_t, _u32, _u32)
+        _sig(L.rpgpu_produce_plan_device, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp)
+        _sig(L.rpgpu_produce_run_device, _i32, _vp, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64,
+             _vp, _vp, _vp, _u64, _vp, _vp, _vp)
         _LIB = L
     return _LIB
 
@@ -448,4 +464,5 @@ EXPORTED = [
     "rpgpu_segidx_track_device", "rpgpu_segidx_write_plan_device", "rpgpu_segidx_write_run_device",
     "rpgpu_segidx_hydrate_device", "rpgpu_segidx_find_device",
     "rpgpu_compaction_tx_scratch_bytes", "rpgpu_compaction_tx_filter_device", "rpgpu_compaction_keep_tx_device",
+    "rpgpu_produce_scratch_bytes", "rpgpu_produce_plan_device", "rpgpu_produce_run_device",
 ]

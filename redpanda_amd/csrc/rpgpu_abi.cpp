@@ -852,6 +852,44 @@ int32_t rpgpu_legacy_run_device(rpgpu_ctx* c, const rpgpu_batch_desc* d_sets, ui
     return RPGPU_OK;
 }
 
+size_t rpgpu_produce_scratch_bytes(uint32_t nrows, uint32_t nrequests) {
+    return rpgpu::produce_scratch_bytes(nrows, nrequests);
+}
+
+int32_t rpgpu_produce_plan_device(rpgpu_ctx* c, const rpgpu_produce_row* d_rows, uint32_t nrows,
+                                  const rpgpu_produce_request* d_requests, uint32_t nrequests, const uint8_t* d_data,
+                                  uint64_t data_bytes, uint64_t* d_out_bytes, uint32_t* d_nbatches, void* d_scratch,
+                                  void* hip_stream) {
+    if (!c || !d_scratch || (nrows && !d_rows) || (nrequests && !d_requests) || (data_bytes && !d_data) ||
+        nrows > 0x40000000u || nrequests > 0x40000000u)
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_produce_plan(d_rows, nrows, d_requests, nrequests, d_data, data_bytes, d_out_bytes,
+                                              d_nbatches, d_scratch, s);
+    if (e != hipSuccess) return fail(c, e, "produce plan launch");
+    return RPGPU_OK;
+}
+
+int32_t rpgpu_produce_run_device(rpgpu_ctx* c, const rpgpu_produce_row* d_rows, uint32_t nrows,
+                                 const rpgpu_produce_request* d_requests, uint32_t nrequests, const uint8_t* d_data,
+                                 uint64_t data_bytes, rpgpu_produce_result* d_req_results,
+                                 rpgpu_produce_batch* d_batches, uint32_t* d_row_batch, uint32_t* d_row_delta,
+                                 uint8_t* d_out, uint64_t out_cap, rpgpu_batch_desc* d_out_descs,
+                                 rpgpu_batch_result* d_out_results, rpgpu_record_index* d_index, uint64_t index_cap,
+                                 uint64_t* d_index_used, void* d_scratch, void* hip_stream) {
+    if (!c || !d_scratch || (nrequests && (!d_requests || !d_req_results)) || (data_bytes && !d_data) ||
+        (nrows && (!d_rows || !d_batches || !d_row_batch || !d_row_delta || !d_out || !d_out_descs || !d_out_results)) ||
+        (reinterpret_cast<uintptr_t>(d_out) & 15u) || nrows > 0x40000000u || nrequests > 0x40000000u)
+        return RPGPU_EINVAL;
+    hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    hipError_t e = rpgpu::launch_produce_run(d_rows, nrows, d_requests, nrequests, d_data, d_req_results, d_batches,
+                                             d_row_batch, d_row_delta, d_out, out_cap, d_out_descs, d_out_results,
+                                             d_index, d_index ? index_cap : 0, d_index_used, d_scratch, c->d_tables,
+                                             c->grid, s);
+    if (e != hipSuccess) return fail(c, e, "produce run launch");
+    return RPGPU_OK;
+}
+
 int32_t rpgpu_legacy_kafka_error_code(const rpgpu_legacy_result* r, const rpgpu_batch_result* out,
                                       uint32_t batch_max_bytes) {
     if (!r) return RPGPU_KAFKA_ERR_UNKNOWN_SERVER_ERROR;

@@ -193,5 +193,18 @@ hipError_t launch_tx_filter(const uint8_t* d_data, const rpgpu_batch_desc* d_des
                             uint32_t nranges, uint8_t* d_discard, rpgpu_tx_stats* d_stats, void* d_scratch,
                             hipStream_t s);
 
+// ---- rpgpu_produce.hip
+size_t produce_scratch_bytes(uint32_t nrows, uint32_t nrequests);
+hipError_t launch_produce_plan(const rpgpu_produce_row* d_rows, uint32_t n, const rpgpu_produce_request* d_requests,
+                               uint32_t nreq, const uint8_t* d_data, uint64_t data_bytes, uint64_t* d_out_bytes,
+                               uint32_t* d_nbatches, void* d_scratch, hipStream_t s);
+hipError_t launch_produce_run(const rpgpu_produce_row* d_rows, uint32_t n, const rpgpu_produce_request* d_requests,
+                              uint32_t nreq, const uint8_t* d_data, rpgpu_produce_result* d_req_results,
+                              rpgpu_produce_batch* d_batches, uint32_t* d_row_batch, uint32_t* d_row_delta,
+                              uint8_t* d_out, uint64_t out_cap, rpgpu_batch_desc* d_out_descs,
+                              rpgpu_batch_result* d_vres2, rpgpu_record_index* d_index, uint64_t index_cap,
+                              uint64_t* d_index_used, void* d_scratch, const uint32_t* d_tables, int grid,
+                              hipStream_t s);
+
 }  // namespace rpgpu
 #endif

@@ -24,7 +24,8 @@
 //                         wave: varints by the message's lane, short keys and
 //                         values in 16-byte pieces; long ones are listed.
 //   legacy_copy_wave_kernel the listed keys and values, a wave each, 16 bytes
-//                         per lane.
+//                         per lane.  (The record writer of both is
+//                         rpgpu_emit.h, shared with rpgpu_produce.hip.)
 //   then the RECRC validation of the rewritten batches (launch_plan /
 //   launch_run) and recrc_patch_kernel, which stores both CRCs
 //   (launch_revalidate, rpgpu_rewrite.h).
@@ -32,6 +33,7 @@
 #include "rpgpu_rewrite.h"
 #include "rpgpu_scan.h"
 #include "rpgpu_legacy.h"
+#include "rpgpu_emit.h"
 
 namespace rpgpu {
 
@@ -39,8 +41,6 @@ namespace {
 
 using rplegacy::Msg;
 using rplegacy::Scan;
-
-constexpr uint32_t kLaneCopyMax = 128;  // longer keys / values are copied by the whole wave
 
 // scratch: totals (64 B) | Scan[n] | slot_sz[n] | slot_off[n] | msg_cnt[n] |
 //          msg_first[n] | recs[n] (u64 each) | ev_key[n] u32 | validation scratch
@@ -82,17 +82,6 @@ __device__ __forceinline__ bool table_fits(const uint64_t* totals, uint64_t out_
 __device__ __forceinline__ uint64_t* work_list(uint8_t* out, const uint64_t* totals) {
     return reinterpret_cast<uint64_t*>(out + table_offset(totals[0]) + totals[1] * sizeof(Msg));
 }
-// the lanes with `want` append `item` to the list: one atomic per wave
-__device__ __forceinline__ void list_append(uint64_t* list, uint64_t* count, bool want, uint64_t item, uint32_t l) {
-    const uint64_t mask = __ballot(want);
-    if (!mask) return;
-    const int first = __builtin_ctzll(mask);
-    uint64_t base = 0;
-    if ((int)l == first) base = atomicAdd(reinterpret_cast<unsigned long long*>(count), (unsigned long long)__builtin_popcountll(mask));
-    base = ((uint64_t)__shfl((uint32_t)(base >> 32), first, 64) << 32) | __shfl((uint32_t)base, first, 64);
-    if (want) list[base + __builtin_popcountll(mask & ((1ull << l) - 1))] = item;
-}
-
 __global__ __launch_bounds__(256) void legacy_scan_kernel(const rpgpu_batch_desc* __restrict__ sets, uint32_t n,
                                                           const uint8_t* __restrict__ data, Parts p, uint8_t* out,
                                                           uint64_t out_cap, int run) {
@@ -135,12 +124,6 @@ __global__ __launch_bounds__(kScanBlock) void legacy_offsets_kernel(Parts p, uin
         if (out_bytes) *out_bytes = msgs ? table_offset(slots) + msgs * kMsgBytes : slots;
         if (records_total) *records_total = recs;
     }
-}
-
-// a value every lane holds, as a wave-uniform one
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    return ((uint64_t)uniform32((uint32_t)(v >> 32)) << 32) | uniform32((uint32_t)v);
 }
 
 // zlib crc32(0, p, len) on one lane: 16 bytes per step, the state folded into
@@ -274,53 +257,13 @@ __global__ __launch_bounds__(256) void legacy_finish_kernel(const rpgpu_batch_de
     out_descs[i] = od;
 }
 
-// 16-byte pieces; the last one ends at the range's end and overlaps the one
-// before it (the same bytes twice), so nothing past either range is touched
-__device__ __forceinline__ void copy_lane(uint8_t* dst, const uint8_t* src, uint32_t len) {
-    if (len < 16) {
-        for (uint32_t k = 0; k < len; k++) dst[k] = src[k];
-        return;
-    }
-    for (uint32_t k = 0; k + 16 <= len; k += 16) {
-        const u32x4 v = ld16(src + k);
-        __builtin_memcpy(dst + k, &v, 16);
-    }
-    if (len & 15u) {
-        const u32x4 v = ld16(src + len - 16);
-        __builtin_memcpy(dst + len - 16, &v, 16);
-    }
-}
-__device__ __forceinline__ void copy_wave(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t l) {
-    for (uint64_t o = 16ull * l; o + 16 <= len; o += 1024) {
-        const u32x4 v = ld16(src + o);
-        __builtin_memcpy(dst + o, &v, 16);
-    }
-    if ((len & 15u) && l == 0) {
-        const u32x4 v = ld16(src + len - 16);
-        __builtin_memcpy(dst + len - 16, &v, 16);
-    }
-}
-
 // where record m's key and value go
-struct RecordPlace {
-    const uint8_t *ksrc, *vsrc;
-    uint8_t *head, *kdst, *vlen_at, *vdst;
-    uint32_t klen, vlen;
-};
 __device__ __forceinline__ RecordPlace place(const Msg& e, const rpgpu_batch_desc* __restrict__ sets,
                                              const uint8_t* __restrict__ data, const rpgpu_legacy_result& r,
                                              uint8_t* out) {
-    RecordPlace q;
     const uint8_t* src = data + sets[e.set].offset;
-    q.head = out + r.out_offset + kHeaderSize + e.rec_off;
-    q.klen = e.key_len > 0 ? (uint32_t)e.key_len : 0u;
-    q.vlen = e.val_len > 0 ? (uint32_t)e.val_len : 0u;
-    q.ksrc = src + e.key_off;
-    q.vsrc = src + e.val_off;
-    q.kdst = q.head + rplegacy::vint_size(e.rec_len) + 2 + rplegacy::vint_size(e.index) + rplegacy::vint_size(e.key_len);
-    q.vlen_at = q.kdst + q.klen;
-    q.vdst = q.vlen_at + rplegacy::vint_size(e.val_len);
-    return q;
+    return place_record(out + r.out_offset + kHeaderSize + e.rec_off, src + e.key_off, src + e.val_off, e.rec_len,
+                        e.index, e.key_len, e.val_len);
 }
 
 // the records of the converted sets, 64 messages per wave: the varints and
@@ -344,13 +287,7 @@ __global__ __launch_bounds__(256) void legacy_emit_kernel(const rpgpu_batch_desc
             const rpgpu_legacy_result& r = lres[e.set];
             if (r.verdict == RPGPU_V_OK) {
                 const RecordPlace q = place(e, sets, data, r, out);
-                (void)rplegacy::put_record_head(q.head, e.rec_len, e.index, e.key_len);
-                (void)rplegacy::put_vint(q.vlen_at, e.val_len);
-                q.vdst[q.vlen] = 0;  // no headers
-                klong = q.klen > kLaneCopyMax;
-                vlong = q.vlen > kLaneCopyMax;
-                if (!klong) copy_lane(q.kdst, q.ksrc, q.klen);
-                if (!vlong) copy_lane(q.vdst, q.vsrc, q.vlen);
+                emit_record_lane(q, e.rec_len, e.index, e.key_len, e.val_len, klong, vlong);
             }
         }
         list_append(list, p.totals + 4, klong, m << 1, l);
@@ -374,8 +311,7 @@ __global__ __launch_bounds__(256) void legacy_copy_wave_kernel(const rpgpu_batch
         const uint64_t item = list[i];
         const Msg e = table[item >> 1];
         const RecordPlace q = place(e, sets, data, lres[e.set], out);
-        if (item & 1) copy_wave((uint8_t*)uniform64((uint64_t)q.vdst), (const uint8_t*)uniform64((uint64_t)q.vsrc), uniform32(q.vlen), l);
-        else copy_wave((uint8_t*)uniform64((uint64_t)q.kdst), (const uint8_t*)uniform64((uint64_t)q.ksrc), uniform32(q.klen), l);
+        copy_listed(q, (item & 1) != 0, l);
     }
 }
 

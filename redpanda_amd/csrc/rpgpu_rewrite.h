@@ -1,5 +1,5 @@
 // rpgpu_rewrite.h — what the kernels that emit new on-disk batches share
-// (decompression, compression, compaction rewrite, legacy conversion).
+// (decompression, compression, compaction rewrite, legacy conversion, produce).
 //
 // A rewriter stores the new body and a header whose two CRC fields are zero,
 // and one output descriptor per batch with RPGPU_OP_RECRC.  launch_revalidate
@@ -67,6 +67,7 @@ __device__ __forceinline__ rpgpu_batch_desc out_desc(uint64_t off, uint32_t leng
 __device__ __forceinline__ bool rewritten(const rpgpu_decomp_result& r) { return r.verdict == RPGPU_V_OK; }
 __device__ __forceinline__ bool rewritten(const rpgpu_legacy_result& r) { return r.verdict == RPGPU_V_OK; }
 __device__ __forceinline__ bool rewritten(const rpgpu_compact_result& r) { return r.out_len != 0; }
+__device__ __forceinline__ bool rewritten(const rpgpu_produce_batch& r) { return r.out_len != 0; }
 
 // stores the CRCs the validation of the rewritten batches computed
 template <class R>

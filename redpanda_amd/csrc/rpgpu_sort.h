@@ -12,7 +12,8 @@
 //   key    the key of item i, for every i < n (never permuted)
 //   in     the pass's input order (null for pass 0: the items' own order)
 //   table  sort_blocks(n) * 256 words of scratch
-// rpgpu_append.hip sorts batches by log; rpgpu_txfilter.hip abort markers by producer.
+// rpgpu_append.hip sorts batches by log; rpgpu_txfilter.hip abort markers by producer;
+// rpgpu_produce.hip rows by partition, then by request.
 #ifndef RPGPU_SORT_H
 #define RPGPU_SORT_H
 
@@ -96,10 +97,13 @@ __global__ __launch_bounds__(kSortBlock) void radix_scatter_kernel(const uint32_
 
 // Sorts the items 0..n-1 on key (keys <= max_key), ping-ponging between idx_a
 // and idx_b; *sorted is the array that holds the result (null when n == 0).
+// in0: the order the first pass reads (null: the items' own), so a sort on a
+// second key chains behind one on a first; in0 must not be idx_a.
 inline hipError_t radix_sort_items(const uint32_t* key, uint32_t n, uint32_t max_key, uint32_t* idx_a,
-                                   uint32_t* idx_b, uint32_t* table, const uint32_t** sorted, hipStream_t s) {
+                                   uint32_t* idx_b, uint32_t* table, const uint32_t** sorted, hipStream_t s,
+                                   const uint32_t* in0 = nullptr) {
     const uint32_t passes = sort_passes(max_key), nb = sort_blocks(n);
-    const uint32_t* in = nullptr;
+    const uint32_t* in = in0;
     for (uint32_t k = 0; n && k < passes; k++) {
         uint32_t* out = (k & 1) ? idx_b : idx_a;
         radix_hist_kernel<<<nb, kSortBlock, 0, s>>>(key, in, n, 8 * k, nb, table);

@@ -190,6 +190,76 @@ class Engine:
             index=d_index.cpu().numpy().view(abi.INDEX_DTYPE)[: min(used, index_cap)].copy(),
             used=used, out_bytes=out_bytes, records_total=records_total)
 
+    # -- produce batches from records (rpgpu_produce_plan_device / rpgpu_produce_run_device) --
+    def produce_records(self, data: np.ndarray, rows: np.ndarray, requests: np.ndarray, out_cap: int | None = None,
+                        runs: int = 1) -> dict:
+        """client::produce_records over many requests: plans, reads back the
+        output size, then runs.  out_cap: the output buffer's size when the
+        caller wants it smaller than the plan asks for (OUT_OVERFLOW).  Returns
+        host copies: req_results, batches (the emitted rows), row_batch,
+        row_delta, out, out_descs / out_results (all nrows rows), index, used,
+        out_bytes, nbatches (the plan's), out_cap."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        rows = np.ascontiguousarray(rows, dtype=abi.PRODUCE_ROW_DTYPE)
+        requests = np.ascontiguousarray(requests, dtype=abi.PRODUCE_REQUEST_DTYPE)
+        n, nreq = len(rows), len(requests)
+        sh = torch.cuda.current_stream(dev).cuda_stream
+        m = max(n, 1)
+
+        def up(a):
+            return torch.from_numpy(np.concatenate([a.view(np.uint8).reshape(-1), np.zeros(1, np.uint8)])).to(dev)
+
+        d_data, d_rows, d_reqs = up(data), up(rows), up(requests)
+        d_tot = torch.zeros(3, dtype=torch.int64, device=dev)  # out_bytes, nbatches, index_used
+        d_scr = torch.zeros(int(self._lib.rpgpu_produce_scratch_bytes(n, nreq)), dtype=torch.uint8, device=dev)
+        rc = self._lib.rpgpu_produce_plan_device(self._ctx, d_rows.data_ptr(), n, d_reqs.data_ptr(), nreq,
+                                                 d_data.data_ptr(), data.nbytes, d_tot.data_ptr(),
+                                                 d_tot.data_ptr() + 8, d_scr.data_ptr(), sh)
+        if rc != abi.RPGPU_OK:
+            raise EngineError(f"rpgpu_produce_plan_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        out_bytes, nbatches = int(d_tot[0].item()), int(d_tot[1].item())
+        if out_cap is None:
+            out_cap = out_bytes + abi.ARENA_TAIL_PAD
+        guard = 256  # behind out_cap: stays 0xa5 (nothing is written past out_cap)
+        d_out = torch.zeros(out_cap + guard, dtype=torch.uint8, device=dev)
+        d_out[out_cap:] = 0xA5
+        d_rres = torch.zeros(max(nreq, 1) * 16, dtype=torch.uint8, device=dev)
+        d_batches = torch.zeros(m * 32, dtype=torch.uint8, device=dev)
+        d_maps = torch.zeros(2 * m, dtype=torch.int32, device=dev)
+        d_odescs = torch.zeros(m * 24, dtype=torch.uint8, device=dev)
+        d_ores = torch.zeros(m * 64, dtype=torch.uint8, device=dev)
+        index_cap = m
+        d_index = torch.zeros(index_cap * 32, dtype=torch.uint8, device=dev)
+        for _ in range(runs):  # a plan may be run any number of times
+            rc = self._lib.rpgpu_produce_run_device(self._ctx, d_rows.data_ptr(), n, d_reqs.data_ptr(), nreq,
+                                                    d_data.data_ptr(), data.nbytes, d_rres.data_ptr(),
+                                                    d_batches.data_ptr(), d_maps.data_ptr(), d_maps.data_ptr() + 4 * m,
+                                                    d_out.data_ptr(), out_cap, d_odescs.data_ptr(), d_ores.data_ptr(),
+                                                    d_index.data_ptr(), index_cap, d_tot.data_ptr() + 16,
+                                                    d_scr.data_ptr(), sh)
+            if rc != abi.RPGPU_OK:
+                raise EngineError(f"rpgpu_produce_run_device: {rc} {self.last_error()}")
+        torch.cuda.synchronize(dev)
+        used = int(d_tot[2].item())
+        req_results = d_rres.cpu().numpy().view(abi.PRODUCE_RESULT_DTYPE)[:nreq].copy()
+        emitted = int(req_results["nbatches"].sum())
+        maps = d_maps.cpu().numpy().view(np.uint32)
+        out = d_out.cpu().numpy()
+        return dict(
+            req_results=req_results,
+            batches=d_batches.cpu().numpy().view(abi.PRODUCE_BATCH_DTYPE)[:emitted].copy(),
+            all_batches=d_batches.cpu().numpy().view(abi.PRODUCE_BATCH_DTYPE)[:n].copy(),
+            row_batch=maps[:n].copy(), row_delta=maps[m:m + n].copy(),
+            out=out[:out_cap].copy(), guard=out[out_cap:].copy(),
+            out_descs=d_odescs.cpu().numpy().view(abi.DESC_DTYPE)[:n].copy(),
+            out_results=d_ores.cpu().numpy().view(abi.RESULT_DTYPE)[:n].copy(),
+            index=d_index.cpu().numpy().view(abi.INDEX_DTYPE)[: min(used, index_cap)].copy(),
+            used=used, out_bytes=out_bytes, nbatches=nbatches, out_cap=out_cap)
+
     # -- decompression (rpgpu_decomp_plan_device / rpgpu_decomp_run_device) -------------
     def decomp_scratch_bytes(self, n: int) -> int:
         """rpgpu_decomp_scratch_bytes_ctx: the scratch this context's decompress calls need."""
